@@ -1,15 +1,23 @@
 #!/usr/bin/env python3
 """bench.py -- image-pairs/s of the full DeMoN forward (bootstrap + 3 x iterative + refine) at 256x192.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
   N > 1:  python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
               --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run sets up (weights, inputs, launch plan, lanes and their calibration), runs W untimed and exactly K timed steps and prints
+the headline line (`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step` = milliseconds of one timed step, `config`).
+`--full` adds everything else below: the single-lane and hoisted-features legs, the output checks, the per-launch roofline entries,
+the host-to-host rates and the CPU baseline (each still has its own --no-* switch).  `--dump-outputs DIR` writes the arrays the
+last timed step computed (what demon_download_outputs hands a caller: predict_* as float32) to DIR/<name>.npy; every lane holds the
+same seeded batch, so the files do not depend on how many lanes the calibration kept, and a dump larger than 64 MB keeps a fixed,
+seeded sample of the pairs (the same pairs in every array).
 
 A "step" is one pass of the hot path over one batch of synthetic pairs already resident in HBM (BASELINE.json
 configs[2]: batch 32 per GPU, full pipeline, hipGraph on) = ONE hipGraph launch.  Steps go round robin over `--lanes` contexts
 of the rank's GPU (demon_amd/lanes.py: own stream, activation arena, resident batch and graph each), so up to that many steps are
-in flight and one pass fills the SIMDs another leaves idle at its kernel boundaries; `single_lane` in the same line is the rate of
-the same K steps on one lane (one step at a time).  Pairs are independent, so ranks shard the
+in flight and one pass fills the SIMDs another leaves idle at its kernel boundaries; `single_lane` in the `--full` line is the rate
+of the same K steps on one lane (one step at a time).  Pairs are independent, so ranks shard the
 batch with no data-path collective (weak scaling: 32 pairs per GPU, configs[3] = 8 x 32); the only
 collective is one RCCL broadcast of the 183 MB weight blob at start-up, outside the timed region.
 Rank 0 prints ONE JSON line.  `roofline` = the single kernel (template instance) with the largest share of the pass by its own time
@@ -199,6 +207,24 @@ def rocprof_stats():
     return {t: {"avg_ms": e["ns"] / e["calls"] * 1e-6, "calls": e["calls"], "source": os.path.basename(paths[-1])} for t, e in out.items() if e["calls"]}
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(outdir, arrays, seed=0):
+    """arrays (pairs on axis 0) -> outdir/<name>.npy as float32; over DUMP_LIMIT_BYTES, a seeded sample of the pairs (sorted, the
+    same pairs in every array) that fits.  Returns the pair indices written."""
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in arrays.items()}
+    n = min(v.shape[0] for v in arrays.values())
+    per_pair = sum(v[0].nbytes for v in arrays.values())
+    keep = np.arange(n)
+    if per_pair * n > DUMP_LIMIT_BYTES:
+        keep = np.sort(np.random.default_rng(seed).choice(n, size=max(1, DUMP_LIMIT_BYTES // per_pair), replace=False))
+    os.makedirs(outdir, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(outdir, k + ".npy"), v[keep])
+    return keep
+
+
 def flush_c_stdio():
     """fflush(NULL): text that native libraries (RCCL's banner) printed through C stdio must not surface after the JSON line"""
     import ctypes
@@ -219,6 +245,11 @@ def main():
     ap.add_argument("--workload", choices=["full", "bootstrap", "hires", "v2"], default="full",
                     help="full = BASELINE configs[2] (default, the metric's configuration); bootstrap = configs[1] "
                          "(batch 8, bootstrap net only); hires = configs[4] (batch 64, 640x480, full pipeline)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline: single-lane and hoisted-features legs, output checks, "
+                         "per-launch roofline, host-to-host rates, CPU baseline (off: set-up, warm-up, timed steps and the result line only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step to DIR/<name>.npy (float32; at most 64 MB, a seeded sample of the pairs beyond)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--no-autotune", action="store_true")
@@ -245,6 +276,8 @@ def main():
                     help="P > 1: the lanes run on P disjoint compute-unit partitions (every lane's streams on the CU mask of partition lane %% P, "
                          "demon_set_cu_mask; --lanes 0 then means one lane per partition); 1: every lane on the whole chip; -1: the shipped default")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
 
     import torch
     from demon_amd import DemonContext, weights as W
@@ -324,10 +357,11 @@ def main():
     from demon_amd.lanes import LaneGroup
     group = LaneGroup(first=ctx, lanes=args.lanes, batch=args.batch, height=height, width=width, device=local_rank, version=version, plan_batch=n,
                       partitions=args.partitions)
-    for li, c in enumerate(group.ctxs[1:], 1):
+    # every lane holds the same batch: the last timed step computes the same outputs whichever lane it ran on (--dump-outputs)
+    for c in group.ctxs[1:]:
         if args.reuse_image_features:
             c.set_option("reuse_image_features", 1)
-        c.upload_inputs(*make_inputs(args.batch, seed=1000 * li + rank, height=height, width=width))
+        c.upload_inputs(pair, img2_2)
     group.run_resident(n, len(group), args.iterations, boot_only)
     group.synchronize()
     lane_rates, lane_mapping = None, None
@@ -362,17 +396,20 @@ def main():
 
     elapsed = timed(lambda k: group.run_resident(n, k, args.iterations, boot_only), group.synchronize)
     local_elapsed = timed.local_s
-    out = ctx.download_outputs(n, with_depth0=not boot_only)
-    finite = all(np.isfinite(v).all() for v in out.values())
-    for c in group.ctxs[1:]:
-        finite = finite and all(np.isfinite(v).all() for v in c.download_outputs(n, with_depth0=not boot_only).values())
+    if args.dump_outputs and rank == 0:   # step i ran on lane i % lanes: the last timed step's outputs are still in its lane
+        dump_outputs(args.dump_outputs, group.ctxs[(args.steps - 1) % len(group)].download_outputs(n, with_depth0=not boot_only))
+    if args.full:
+        out = ctx.download_outputs(n, with_depth0=not boot_only)
+        finite = all(np.isfinite(v).all() for v in out.values())
+        for c in group.ctxs[1:]:
+            finite = finite and all(np.isfinite(v).all() for v in c.download_outputs(n, with_depth0=not boot_only).values())
     # The same K steps with the image-only layers of the iterative nets hoisted out of the iteration loop (option reuse_image_features:
     # conv1 / conv2 of netFlow2 / netDM2 see image_pair and their weights only, so one evaluation serves all iterations of a pass --
     # bit-identical outputs, 16 launches and 1.77 GFLOP per pair fewer).  NOT the headline: `value` executes every layer of every
     # iteration, like the reference's three IterativeNet.eval calls (examples/example.py:87-99) do; this is what a caller of demon_full gets
     # by setting the option.
     elapsed_hoisted, hoisted_identical = None, None
-    if not boot_only and args.iterations > 1 and not args.reuse_image_features and not args.no_hoisted_leg:
+    if args.full and not boot_only and args.iterations > 1 and not args.reuse_image_features and not args.no_hoisted_leg:
         for c in group.ctxs:
             c.set_option("reuse_image_features", 1)
         group.run_resident(n, len(group), args.iterations, boot_only)   # (every lane captures the other graph outside the timed region)
@@ -383,36 +420,37 @@ def main():
         for c in group.ctxs:
             c.set_option("reuse_image_features", 0)
     group.close()          # lane 0 = ctx stays (and gets its side branches back)
-    shipped_plans = not args.no_autotune and not args.retune
-    if args.lanes > 1 and shipped_plans:
-        ctx.load_tuned_plan(n)   # ... and the plan tuned for one pass at a time, when the lanes ran a throughput-mode plan
-    # the same K steps one at a time on one lane (round 1-3's protocol), for comparison
-    # (re-measured even when the calibration kept ONE lane, unless that lane already ran the latency plan with its side branches on)
-    single_is_headline = args.lanes == 1 and not (shipped_plans and plan_lanes > 1) and ctx.get_option("side_branches") == 1
-    if distributed:   # timed() holds collectives: every rank re-times or none does (a rank whose calibration kept one lane must not skip alone)
-        flag = torch.tensor([1 if single_is_headline else 0], dtype=torch.int32, device="cuda")
-        dist.all_reduce(flag, op=dist.ReduceOp.MIN)
-        single_is_headline = bool(flag.item())
-    elapsed_single = elapsed if single_is_headline else timed(
-        lambda k: [ctx.run_bootstrap(n) if boot_only else ctx.run_full(n, args.iterations) for _ in range(k)], ctx.synchronize)
-    local_single = timed.local_s
-    # every rank's own numbers (its clock, its calibration): the first multi-GPU run must be diagnosable from the one JSON line
-    mine = {"rank": rank, "pairs_per_s": args.batch * args.steps / local_elapsed, "single_lane_pairs_per_s": args.batch * args.steps / local_single,
-            "lanes": args.lanes, "lanes_mapping": lane_mapping, "host_placement": placement,
-            "lanes_calibration_pairs_per_s": {str(k): round(v, 1) for k, v in lane_rates.items()} if lane_rates else None}
-    per_rank = [mine]
-    if distributed:
-        try:
-            gathered = [None] * world
-            dist.all_gather_object(gathered, mine)
-            per_rank = gathered
-        except Exception as e:      # diagnostics must never cost the run its JSON line
-            mine["gather_error"] = repr(e)[:200]
-    out1 = ctx.download_outputs(n, with_depth0=not boot_only)
-    if args.lanes > 1 and shipped_plans:
-        ctx.load_tuned_plan(n, lanes=plan_lanes, partitions=args.partitions)   # the per-launch profile below is of the kernels the headline ran
-    # (bit-identical when both runs used the same launch plan; a throughput-mode plan sums in another order)
-    lanes_vs_single = max(float(np.abs(out[k].astype(np.float64) - out1[k]).sum() / max(np.abs(out1[k]).sum(), 1e-30)) for k in out)
+    if args.full:
+        shipped_plans = not args.no_autotune and not args.retune
+        if args.lanes > 1 and shipped_plans:
+            ctx.load_tuned_plan(n)   # ... and the plan tuned for one pass at a time, when the lanes ran a throughput-mode plan
+        # the same K steps one at a time on one lane (round 1-3's protocol), for comparison
+        # (re-measured even when the calibration kept ONE lane, unless that lane already ran the latency plan with its side branches on)
+        single_is_headline = args.lanes == 1 and not (shipped_plans and plan_lanes > 1) and ctx.get_option("side_branches") == 1
+        if distributed:   # timed() holds collectives: every rank re-times or none does (a rank whose calibration kept one lane must not skip alone)
+            flag = torch.tensor([1 if single_is_headline else 0], dtype=torch.int32, device="cuda")
+            dist.all_reduce(flag, op=dist.ReduceOp.MIN)
+            single_is_headline = bool(flag.item())
+        elapsed_single = elapsed if single_is_headline else timed(
+            lambda k: [ctx.run_bootstrap(n) if boot_only else ctx.run_full(n, args.iterations) for _ in range(k)], ctx.synchronize)
+        local_single = timed.local_s
+        # every rank's own numbers (its clock, its calibration): the first multi-GPU run must be diagnosable from the one JSON line
+        mine = {"rank": rank, "pairs_per_s": args.batch * args.steps / local_elapsed, "single_lane_pairs_per_s": args.batch * args.steps / local_single,
+                "lanes": args.lanes, "lanes_mapping": lane_mapping, "host_placement": placement,
+                "lanes_calibration_pairs_per_s": {str(k): round(v, 1) for k, v in lane_rates.items()} if lane_rates else None}
+        per_rank = [mine]
+        if distributed:
+            try:
+                gathered = [None] * world
+                dist.all_gather_object(gathered, mine)
+                per_rank = gathered
+            except Exception as e:      # diagnostics must never cost the run its JSON line
+                mine["gather_error"] = repr(e)[:200]
+        out1 = ctx.download_outputs(n, with_depth0=not boot_only)
+        if args.lanes > 1 and shipped_plans:
+            ctx.load_tuned_plan(n, lanes=plan_lanes, partitions=args.partitions)   # the per-launch profile below is of the kernels the headline ran
+        # (bit-identical when both runs used the same launch plan; a throughput-mode plan sums in another order)
+        lanes_vs_single = max(float(np.abs(out[k].astype(np.float64) - out1[k]).sum() / max(np.abs(out1[k]).sum(), 1e-30)) for k in out)
 
     result = None
     if rank == 0:
@@ -436,16 +474,19 @@ def main():
                        "weights_broadcast_ms": round(1e3 * t_bcast, 2), "weights_broadcast_route": bcast_route,
                        "rccl_nranks": rccl_nranks,
                        "launch_plan": plan_src, "plan_setup_s": round(t_tune, 2)},
-            "outputs_finite": bool(finite),
-            # one batch at a time on one lane (rounds 1-3's protocol, BASELINE configs[2] read strictly): the like-for-like trend number
-            "value_single_lane": pairs / elapsed_single,
-            "per_rank": {"pairs_per_s_min": min(r["pairs_per_s"] for r in per_rank), "pairs_per_s_max": max(r["pairs_per_s"] for r in per_rank),
-                         "single_lane_pairs_per_s_min": min(r["single_lane_pairs_per_s"] for r in per_rank),
-                         "lanes": [r["lanes"] for r in per_rank], "ranks": per_rank},
-            "single_lane": {"pairs_per_s": pairs / elapsed_single, "ms_per_step": 1e3 * elapsed_single / args.steps,
-                            "lane0_outputs_rel_l1": lanes_vs_single, "lane0_outputs_match": bool(lanes_vs_single <= 1e-4),
-                            "note": "the same K steps one at a time on one lane (side branches of the pass on a second stream, as in rounds 1-3)"},
         }
+        if args.full:
+            result.update({
+                "outputs_finite": bool(finite),
+                # one batch at a time on one lane (rounds 1-3's protocol, BASELINE configs[2] read strictly): the like-for-like trend number
+                "value_single_lane": pairs / elapsed_single,
+                "per_rank": {"pairs_per_s_min": min(r["pairs_per_s"] for r in per_rank), "pairs_per_s_max": max(r["pairs_per_s"] for r in per_rank),
+                             "single_lane_pairs_per_s_min": min(r["single_lane_pairs_per_s"] for r in per_rank),
+                             "lanes": [r["lanes"] for r in per_rank], "ranks": per_rank},
+                "single_lane": {"pairs_per_s": pairs / elapsed_single, "ms_per_step": 1e3 * elapsed_single / args.steps,
+                                "lane0_outputs_rel_l1": lanes_vs_single, "lane0_outputs_match": bool(lanes_vs_single <= 1e-4),
+                                "note": "the same K steps one at a time on one lane (side branches of the pass on a second stream, as in rounds 1-3)"},
+            })
         if gflop_pair:
             result["pipeline_mfma_frac"] = value / world * gflop_pair * 1e9 / (PEAK_FP32_MFMA_TFLOPS * 1e12)
         if elapsed_hoisted:
@@ -455,7 +496,7 @@ def main():
                 "note": "NOT the headline: the same lanes and steps with option reuse_image_features (conv1 / conv2 of the iterative nets depend on image_pair "
                         "and weights only and are evaluated once per pass instead of once per iteration: 16 launches fewer); `value` executes every layer "
                         "of every iteration like the reference's three eval calls"}
-        if not args.no_roofline and not boot_only:
+        if args.full and not args.no_roofline and not boot_only:
             recs = ctx.profile_full(n, args.iterations, repeats=3)
             # the same launches "in flight": every step timed as L concurrent replays on L streams (demon_profile_full under option
             # tune_lanes; a launch is charged 1 / (5 L) of the time 5 launches x L streams take) -- what a launch costs in the regime
@@ -631,7 +672,7 @@ def main():
                     tf = r["flops"] / (r["ms"] * 1e-3) / 1e12 if r["ms"] > 0 else 0.0
                     gbs = r["bytes"] / (r["ms"] * 1e-3) / 1e9 if r["ms"] > 0 else 0.0
                     print("%-44s %-30s %8.3f ms %8.2f TF/s %9.1f GB/s" % (r["name"], r["kernel"], r["ms"], tf, gbs), file=sys.stderr)
-        if not args.no_e2e and not boot_only:
+        if args.full and not args.no_e2e and not boot_only:
             # second number of SURVEY 8(d) "GPU timing": host buffers in, host buffers out (H2D of image_pair + image2_2,
             # the whole pipeline, D2H of every output; synchronous pageable copies) -- never `value`
             reps = max(3, min(10, args.steps))
@@ -645,11 +686,11 @@ def main():
             result["extra"] = {"end_to_end_pairs_per_s": n / dt, "end_to_end_ms_per_step": 1e3 * dt,
                                "h2d_bytes_per_step": in_b, "d2h_bytes_per_step": out_b,
                                "note": "demon_full from / to pageable numpy buffers on rank 0, synchronous copies (PCIe-inclusive; not the metric)"}
-        if not args.no_cpu_baseline and world == 1 and args.workload == "full":
+        if args.full and not args.no_cpu_baseline and world == 1 and args.workload == "full":
             os.sched_setaffinity(0, affinity0)        # the baseline gets every host core the process started with
             result["cpu_baseline"] = cpu_baseline(host_weights)
     ctx.close()
-    if rank == 0 and not args.no_e2e and args.workload in ("full", "v2"):
+    if rank == 0 and args.full and not args.no_e2e and args.workload in ("full", "v2"):
         # (after this rank's context is gone: the lanes of the pipeline then get the stream -> hardware-queue mapping of a process of
         # their own, which is what a batch-streaming caller has)
         # the host-to-host rate a batch-streaming caller gets (examples/evaluation.py:225-256 fed in batches): two contexts /

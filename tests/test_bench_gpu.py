@@ -6,6 +6,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -34,7 +35,7 @@ def _env(**extra):
 
 def test_bench_under_torch_distributed_run_with_the_rccl_route():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
-           "--master-port", "29571", "bench.py", "--gpus", "1", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-roofline", "--no-e2e"]
+           "--master-port", "29571", "bench.py", "--gpus", "1", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-roofline", "--no-e2e"]
     r = subprocess.run(cmd, cwd=ROOT, env=_env(DEMON_FORCE_DIST="1"), capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-3000:])
     lines = [l for l in r.stdout.splitlines() if l.strip()]
@@ -57,8 +58,8 @@ def test_bench_under_torch_distributed_run_with_the_rccl_route():
 
 
 def test_bench_default_line_has_roofline_and_host_to_host_rates():
-    """the line the driver records (cpu_baseline left out here: it is 30 s of host work and has its own protocol)"""
-    r = subprocess.run([sys.executable, "bench.py", "--steps", "5", "--warmup", "2", "--no-cpu-baseline"], cwd=ROOT, env=_env(),
+    """the --full line (cpu_baseline left out here: it is 30 s of host work and has its own protocol)"""
+    r = subprocess.run([sys.executable, "bench.py", "--steps", "5", "--warmup", "2", "--full", "--no-cpu-baseline"], cwd=ROOT, env=_env(),
                        capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-3000:])
     recs = _json_lines(r.stdout)
@@ -98,6 +99,33 @@ def test_bench_default_line_has_roofline_and_host_to_host_rates():
     assert p["pinned"] is True and p["outputs_equal_resident_run"] is True and 2 <= p["contexts"] <= 5
     assert p["pairs_per_s"] > x["end_to_end_pairs_per_s"]                                  # overlap beats synchronous pageable copies
     assert 0.5 < p["frac_of_resident"] < 1.5      # (two batches in flight hide per-launch latencies: the pipelined rate may exceed the one-stream rate)
+
+
+def test_plain_bench_line_and_dumped_outputs(tmp_path, gpu_ctx):
+    """a plain run: the headline line only, exactly --steps timed steps, and --dump-outputs writes what the last timed step computed
+    on the seeded batch (every lane holds the same pairs, so the files do not depend on the lane count the calibration kept)"""
+    from conftest import make_inputs, rel_l1
+    d = tmp_path / "dump"
+    r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1", "--dump-outputs", str(d)], cwd=ROOT, env=_env(),
+                       capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-3000:])
+    recs = _json_lines(r.stdout)
+    assert len(recs) == 1
+    rec = recs[0]
+    assert rec["metric"] == "image-pairs/s full 3-iter DeMoN forward @256x192" and rec["unit"] == "pairs/s"
+    assert rec["higher_is_better"] is True and rec["dtype"] == "f32" and rec["steps"] == 3 and rec["warmup"] == 1
+    assert abs(rec["value"] - 32 * 3 / (rec["ms_per_step"] * 3e-3)) < 1e-6 * rec["value"]
+    for key in ("roofline", "single_lane", "image_features_hoisted", "extra", "cpu_baseline", "per_rank"):
+        assert key not in rec, key                                                      # measured by --full only
+    got = {p.name[:-4]: np.load(str(p)) for p in d.iterdir()}
+    assert all(v.dtype == np.float32 and v.shape[0] == 32 and np.isfinite(v).all() for v in got.values())
+    assert sum(v.nbytes for v in got.values()) <= 64 << 20
+    pair, img2_2 = make_inputs(32, seed=0)                                              # bench.py's batch of rank 0
+    for i in range(0, 32, 4):
+        want = gpu_ctx.full(pair[i:i + 4], img2_2[i:i + 4], iterations=3)               # what a caller of demon_full receives
+        assert sorted(got) == sorted(want), (sorted(got), sorted(want))
+        for k, v in got.items():
+            assert rel_l1(v[i:i + 4], want[k]) < 1e-3, (k, i, rel_l1(v[i:i + 4], want[k]))
 
 
 def test_headline_protocol_parity_under_torch_distributed_run():
