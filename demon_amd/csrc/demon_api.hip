@@ -91,6 +91,21 @@ struct Layer {
         if (kh == 1 && sh != 1) return -1;
         return wino1d_kind(kw == 1 ? kh : kw, kw == 1 ? sh : sw);
     }
+    // option precision = 1 (conv_bf16.hip): the layers with Cin >= 16 and Cout >= 8 (but motion_fc2, which runs inside the fp32
+    // motion_tail launch) run on the bf16 matrix cores, with a K padding of their own (Kb, a multiple of kBf16K), its K table and the
+    // weights as bf16 [cls][Kb / 8][Mpad][8], refreshed from d_wp whenever that changes.  Allocated on the first use of the mode.
+    const int *precision = nullptr;   // the owning context's option (null: always fp32)
+    int Kb = 0;
+    KEntry *d_ktab_b = nullptr;
+    void *d_wb = nullptr;
+    mutable bool wb_dirty = true;
+    bool bf16_eligible() const
+    {
+        static const std::string fc2 = "/motion_fc2";
+        const bool is_fc2 = name.size() >= fc2.size() && name.compare(name.size() - fc2.size(), fc2.size(), fc2) == 0;
+        return Cin >= 16 && Cout >= 8 && !is_fc2;
+    }
+    bool bf16_on() const { return precision && *precision == 1 && bf16_eligible(); }
     bool have_kernel = false, have_bias = false;
     std::vector<int64_t> kernel_dims;  // TF layout
     int force_tile = -1, force_split = 0;  // tuning override (demon_bench_layer)
@@ -190,6 +205,7 @@ struct demon_ctx {
     int opt_side_branches = 1;
     int opt_fused_pairs = 1;  // conv_pair.hip for the pairs conv_pair_applies() selects
     int opt_fused_inputs = 1;  // one launch for the extra-input assembly of the iterative blocks / the refinement input
+    int opt_precision = 0;     // 0: fp32; 1: bf16 operands on the eligible layers (Layer::bf16_eligible, conv_bf16.hip)
     // all packed kernels and biases of the networks live in ONE device slab (alloc_weight_slab), so that
     // demon_broadcast_weights is a single RCCL broadcast of device-resident, already packed data
     float *w_slab = nullptr;
@@ -311,23 +327,11 @@ void add_variable(demon_ctx *c, Layer *L, bool is_bias)
 }
 
 // ---- layer planning (geometry, K table) ------------------------------------------------------------
-bool plan_layer(demon_ctx *c, Layer *L, bool alloc_weights = true)
+// the implicit-GEMM K table [cls][Kpad] of a planned layer (rows k >= K: padding)
+std::vector<KEntry> make_ktab(const Layer *L, int Kpad)
 {
     const int H = L->in.H, W = L->in.W;
-    std::vector<KEntry> tab;
-    if (L->kind == Layer::CONV) {
-        L->K = L->kh * L->kw * L->Cin;
-        L->ncls = 1;
-    } else if (L->kind == Layer::DECONV) {
-        L->K = 4 * L->Cin;
-        L->ncls = 4;
-    } else {
-        L->K = L->Cin;
-        L->ncls = 1;
-    }
-    L->Kpad = round_up(L->K, 16);
-    L->Mpad = round_up(L->Cout, 32);
-    tab.assign((size_t)L->ncls * L->Kpad, KEntry{0, (int)((unsigned)(-30000) << 16)});
+    std::vector<KEntry> tab((size_t)L->ncls * Kpad, KEntry{0, (int)((unsigned)(-30000) << 16)});
     auto pack = [](int dy, int dx) { return (int)(((unsigned)dy << 16) | ((unsigned)dx & 0xffffu)); };
     if (L->kind == Layer::CONV) {
         for (int a = 0; a < L->kh; ++a)
@@ -348,12 +352,31 @@ bool plan_layer(demon_ctx *c, Layer *L, bool alloc_weights = true)
                     for (int ci = 0; ci < L->Cin; ++ci) {
                         const int k = (ty * 2 + tx) * L->Cin + ci;
                         const int dy = tap_d[py][ty], dx = tap_d[px][tx];
-                        tab[(size_t)cls * L->Kpad + k] = KEntry{ci * H * W + dy * W + dx, pack(dy, dx)};
+                        tab[(size_t)cls * Kpad + k] = KEntry{ci * H * W + dy * W + dx, pack(dy, dx)};
                     }
         }
     } else {
         for (int k = 0; k < L->K; ++k) tab[k] = KEntry{k, pack(0, 0)};
     }
+    return tab;
+}
+
+bool plan_layer(demon_ctx *c, Layer *L, bool alloc_weights = true)
+{
+    const int H = L->in.H, W = L->in.W;
+    if (L->kind == Layer::CONV) {
+        L->K = L->kh * L->kw * L->Cin;
+        L->ncls = 1;
+    } else if (L->kind == Layer::DECONV) {
+        L->K = 4 * L->Cin;
+        L->ncls = 4;
+    } else {
+        L->K = L->Cin;
+        L->ncls = 1;
+    }
+    L->Kpad = round_up(L->K, 16);
+    L->Mpad = round_up(L->Cout, 32);
+    const std::vector<KEntry> tab = make_ktab(L, L->Kpad);
     L->d_ktab = (KEntry *)dev_alloc(c, tab.size() * sizeof(KEntry));
     L->Krows = L->Kpad + 16;  // 16 zero rows of slack: the patch kernel's last channel chunk may read past K
     if (!L->d_ktab) return false;
@@ -458,6 +481,7 @@ int upload_kernel(demon_ctx *c, Layer *L, const float *w)
     HIP_TRY(c, hipMemcpy(L->d_wp, wp.data(), wp.size() * sizeof(float), hipMemcpyHostToDevice));
     L->have_kernel = true;
     L->wf_dirty = true;
+    L->wb_dirty = true;
     L->w1_dirty = true;
     L->w3_dirty = true;
     L->w4_dirty = true;
@@ -465,6 +489,18 @@ int upload_kernel(demon_ctx *c, Layer *L, const float *w)
     return DEMON_OK;
 }
 
+// option precision = 1: the bf16 K table and weight buffer of an eligible layer, on its first use in that mode (never inside a capture)
+bool alloc_bf16(demon_ctx *c, Layer *L)
+{
+    if (L->d_wb) return true;
+    L->Kb = round_up(L->K, kBf16K);
+    const std::vector<KEntry> tab = make_ktab(L, L->Kb);
+    L->d_ktab_b = (KEntry *)dev_alloc(c, tab.size() * sizeof(KEntry));
+    if (!L->d_ktab_b || hipMemcpy(L->d_ktab_b, tab.data(), tab.size() * sizeof(KEntry), hipMemcpyHostToDevice) != hipSuccess) return false;
+    L->d_wb = dev_alloc(c, sizeof(uint16_t) * (size_t)L->ncls * L->Kb * L->Mpad);
+    L->wb_dirty = true;
+    return L->d_wb != nullptr;
+}
 
 float *alloc_splitk_workspace(demon_ctx *c)
 {
@@ -711,6 +747,10 @@ void refresh_stream_weights(const Layer *L, hipStream_t s)
     if (L->d_wd && L->wd_dirty) {   // re-blocked weights of the weight-streaming dense kernel (dense_stream.hip)
         launch_dense_repack(L->d_wd, L->d_wp, L->Cin, L->Mpad, s);
         L->wd_dirty = false;
+    }
+    if (L->d_wb && L->wb_dirty) {   // bf16 weights of conv_bf16.hip (option precision = 1)
+        launch_bf16_repack(L->d_wb, L->d_wp, L->ncls, L->K, L->Kb, L->Mpad, (long)L->Krows * L->Mpad, s);
+        L->wb_dirty = false;
     }
     if (!L->d_wf || !L->wf_dirty) return;
     launch_stream_repack(L->d_wf, L->d_wp, L->ncls, L->K, L->Mpad, (long)L->Krows * L->Mpad, s);
@@ -967,6 +1007,26 @@ void run_mfma(const ConvArgs &a_in, ConvPlan plan, int ncls, hipStream_t s)
     g_last_kernel = g_kernel_tag;
 }
 
+// option precision = 1 (conv_bf16.hip), an eligible layer: the heuristic plan, whatever the layer's (fp32) plan entry says.  Test hook:
+// DEMON_FORCE_PLAN="17,tile,ksplit" forces a tile and split-K (honoured only here, i.e. in bf16 mode)
+template <class Clamp>
+void run_bf16(const Layer *L, ConvArgs a, long P, float *ws, hipStream_t s, Clamp clamp_split)
+{
+    refresh_stream_weights(L, s);   // (a no-op for network layers: prepare_stream_weights ran before any capture)
+    a.ktab = L->d_ktab_b;
+    a.Kpad = L->Kb;
+    ConvPlan plan = choose_bf16_plan(L->Mpad, P, L->ncls, L->Kb, ws ? kSplitKWorkspaceFloats : 0);
+    if (const char *fp = getenv("DEMON_FORCE_PLAN")) {
+        int kind = 0, tile = 0, ks = 1;
+        if (sscanf(fp, "%d,%d,%d", &kind, &tile, &ks) == 3 && kind == 17 && tile >= 0 && tile < TILE_COUNT && L->Mpad % conv_tile_bm(tile) == 0)
+            plan = ConvPlan{tile, std::max(1, std::min(ks, L->Kb / kBf16K))};
+    }
+    plan.ksplit = clamp_split(plan.ksplit);
+    launch_conv_bf16(a, L->d_wb, plan, L->ncls, s);
+    snprintf(g_kernel_tag, sizeof g_kernel_tag, "conv_bf16<%dx%d>%s", conv_tile_bm(plan.tile), conv_tile_bn(plan.tile), split_suffix(plan.ksplit));
+    g_last_kernel = g_kernel_tag;
+}
+
 void run_layer(const Layer *L, int n, hipStream_t s, float *ws)
 {
     ConvArgs a;
@@ -977,12 +1037,15 @@ void run_layer(const Layer *L, int n, hipStream_t s, float *ws)
         while (k > 1 && (!ws || (long)L->ncls * k * L->Mpad * P > kSplitKWorkspaceFloats)) --k;
         return k;
     };
+    if (L->bf16_on()) { run_bf16(L, a, P, ws, s, clamp_split); return; }
     // test hook: DEMON_FORCE_PLAN="kind,tile,ksplit" forces one kernel variant for every layer it applies to
     if (const char *fp = getenv("DEMON_FORCE_PLAN")) {
         int kind = 0, tile = 0, ks = 1;
         if (sscanf(fp, "%d,%d,%d", &kind, &tile, &ks) == 3) {
             if (kind == 3) {
                 if (small_applies(L)) { run_small(L, a, s); return; }
+            } else if (kind == 17) {
+                // conv_bf16 (run_bf16): nothing to force in fp32 mode
             } else if (kind == 4) {
                 if (L->stream_ok() && tile >= 0 && tile < STREAM_VARIANTS && L->Mpad % stream_variant_bm(tile) == 0) {
                     run_stream(L, a, tile, clamp_split(ks), s);
@@ -1376,6 +1439,7 @@ struct Builder {
         L->kh = kh; L->kw = kw; L->sh = sh; L->sw = sw; L->ph = kh / 2; L->pw = kw / 2; L->act = act;
         if (same) { L->ph = kh > sh ? (kh - sh) / 2 : 0; L->pw = kw > sw ? (kw - sw) / 2 : 0; }
         L->in = in; L->out = out; L->scale = scale;
+        L->precision = &c->opt_precision;
         if (kind == Layer::CONV) L->kernel_dims = {kh, kw, in.C, out.C};
         else if (kind == Layer::DECONV) L->kernel_dims = {4, 4, out.C, in.C};
         else L->kernel_dims = {in.C, out.C};
@@ -1436,7 +1500,8 @@ struct Builder {
         std::function<bool(int)> applies;
         if (chainable) {
             c->chain_pairs.push_back({Ly, Lx});
-            applies = [Ly, Lx](int n) { int kind, v; return chain_choice(Ly, Lx, n, kind, v); };
+            // (bf16 mode: a pair with an eligible layer runs as its two layers)
+            applies = [Ly, Lx](int n) { int kind, v; return !Ly->bf16_on() && !Lx->bf16_on() && chain_choice(Ly, Lx, n, kind, v); };
             st.bytes_per_sample += 8.0 * (double)cy * Hmid * in.W;  // the intermediate is still written, and read back out of L2
             st.fn = [Ly, Lx, ws](int n, hipStream_t s2) {
                 int kind, v;
@@ -1447,7 +1512,11 @@ struct Builder {
         } else {
             // plan kind 12 on the k x 1 layer (conv_thin.hip): the pair runs as its two layers, not as the fused launch
             c->fused_pairs.push_back({Ly, Lx});
-            applies = [Ly](int n) { auto it = nearest_tuned(Ly, n); return !(it != Ly->tuned.end() && it->second.kind == 12 && thin_applies(Ly)); };
+            applies = [Ly, Lx](int n) {
+                if (Ly->bf16_on() || Lx->bf16_on()) return false;
+                auto it = nearest_tuned(Ly, n);
+                return !(it != Ly->tuned.end() && it->second.kind == 12 && thin_applies(Ly));
+            };
             st.fn = [Ly, Lx, ws](int n, hipStream_t s2) {
                 if (run_pair(Ly, Lx, n, s2)) return;
                 run_layer(Ly, n, s2, ws);
@@ -1895,6 +1964,15 @@ void enqueue_sequence(demon_ctx *c, int kind, int n, int iterations, hipStream_t
     if (kind == SEQ_REFINE || kind == SEQ_FULL) run_steps(c, c->net_refine, n, s, 0, ev);
 }
 
+// the options that change what a sequence enqueues (keys of the captured graphs)
+std::string option_key(const demon_ctx *c)
+{
+    char key[64];
+    snprintf(key, sizeof key, "%d:%d:%d:%d:%d:%d", c->opt_f2d_method, c->opt_reuse_image, c->opt_side_branches, c->opt_fused_pairs,
+             c->opt_fused_inputs, c->opt_precision);
+    return key;
+}
+
 // one hipGraph per (sequence, batch, iterations): the whole kernel chain becomes a single launch
 int run_sequence(demon_ctx *c, int kind, int n, int iterations)
 {
@@ -1907,9 +1985,8 @@ int run_sequence(demon_ctx *c, int kind, int n, int iterations)
         }
         return DEMON_OK;
     }
-    char key[64];
-    snprintf(key, sizeof key, "%d:%d:%d:%d:%d:%d:%d:%d", kind, n, iterations, c->opt_f2d_method, c->opt_reuse_image, c->opt_side_branches,
-             c->opt_fused_pairs, c->opt_fused_inputs);
+    char key[80];
+    snprintf(key, sizeof key, "%d:%d:%d:%s", kind, n, iterations, option_key(c).c_str());
     auto it = c->graphs.find(key);
     if (it == c->graphs.end()) {
         hipGraph_t graph = nullptr;
@@ -1926,10 +2003,18 @@ int run_sequence(demon_ctx *c, int kind, int n, int iterations)
     return DEMON_OK;
 }
 
-// fragment-order copies of the weights (conv_stream.hip) follow every weight change; done here, before a sequence is captured
-void prepare_stream_weights(demon_ctx *c)
+// fragment-order copies of the weights (conv_stream.hip) follow every weight change; done here, before a sequence is captured.  In bf16
+// mode the eligible layers' bf16 weights too (allocated here on the first use of the mode).  false: an allocation failed (c->err says which)
+bool prepare_stream_weights(demon_ctx *c)
 {
-    for (auto &L : c->layers) refresh_stream_weights(L.get(), c->stream);
+    for (auto &L : c->layers) {
+        if (L->bf16_on() && !alloc_bf16(c, L.get())) {
+            fail(c, DEMON_ERR_HIP, "device allocation failed (bf16 weights of " + L->name + ")");
+            return false;
+        }
+        refresh_stream_weights(L.get(), c->stream);
+    }
+    return true;
 }
 
 // a context's stream: on its CU mask when it has one (demon_set_cu_mask), else a plain non-blocking stream
@@ -1956,7 +2041,7 @@ int check_batch(demon_ctx *c, int n)
     std::string missing;
     if (!weights_ready(c, &missing)) return fail(c, DEMON_ERR_NOT_READY, "weights not set for layer " + missing);
     hipSetDevice(c->device);
-    prepare_stream_weights(c);
+    if (!prepare_stream_weights(c)) return DEMON_ERR_HIP;
     return DEMON_OK;
 }
 
@@ -2339,7 +2424,7 @@ void slab_arrived(demon_ctx *c)
 {
     for (auto &g : c->graphs) hipGraphExecDestroy(g.second);
     c->graphs.clear();
-    for (auto &L : c->layers) { L->have_kernel = L->have_bias = true; L->wf_dirty = true; L->w1_dirty = true; L->w3_dirty = true; L->w4_dirty = true; L->wd_dirty = true; }
+    for (auto &L : c->layers) { L->have_kernel = L->have_bias = true; L->wf_dirty = true; L->wb_dirty = true; L->w1_dirty = true; L->w3_dirty = true; L->w4_dirty = true; L->wd_dirty = true; }
 }
 }  // namespace
 extern "C" {
@@ -2436,6 +2521,11 @@ int demon_set_option(demon_ctx *c, const char *key, int value)
         return DEMON_OK;
     }
     if (!strcmp(key, "side_branches")) { c->opt_side_branches = (value && c->side_stream && c->d_ws_side != c->d_ws) ? 1 : 0; return DEMON_OK; }
+    if (!strcmp(key, "precision")) {
+        if (value != 0 && value != 1) return fail(c, DEMON_ERR_INVALID, "precision must be 0 (fp32) or 1 (bf16)");
+        c->opt_precision = value;
+        return DEMON_OK;
+    }
     return fail(c, DEMON_ERR_NOT_FOUND, std::string("unknown option ") + key);
 }
 
@@ -2449,6 +2539,7 @@ int demon_get_option(const demon_ctx *c, const char *key, int *value)
     else if (!strcmp(key, "fused_inputs")) *value = c->opt_fused_inputs;
     else if (!strcmp(key, "tune_lanes")) *value = c->opt_tune_lanes;
     else if (!strcmp(key, "side_branches")) *value = c->opt_side_branches;
+    else if (!strcmp(key, "precision")) *value = c->opt_precision;
     else return DEMON_ERR_NOT_FOUND;
     return DEMON_OK;
 }
@@ -2508,6 +2599,13 @@ int demon_autotune(demon_ctx *c, int n)
     hipSetDevice(c->device);
     for (auto &g : c->graphs) hipGraphExecDestroy(g.second);  // captured launches embed the old choices
     c->graphs.clear();
+    // plans describe the fp32 path: the layers are measured in fp32 whatever the context's precision
+    struct KeepPrecision {
+        demon_ctx *c;
+        int saved;
+        ~KeepPrecision() { c->opt_precision = saved; }
+    } keep{c, c->opt_precision};
+    c->opt_precision = 0;
     prepare_stream_weights(c);
     // DEMON_TUNE_ONLY=<substring>[,<substring> ...]: re-tune only the layers whose name contains one of them (the others keep their installed plan entries)
     const char *only_env = getenv("DEMON_TUNE_ONLY");
@@ -2786,7 +2884,7 @@ int demon_lanes_run_group(demon_ctx *const *ctxs, int nctx, int n, int iteration
         if ((r = check_batch(ctxs[i], n))) return i ? fail(c0, r, "lane " + std::to_string(i) + ": " + ctxs[i]->err) : r;
     hipSetDevice(c0->device);
     std::string key = std::to_string(bootstrap_only ? 1 : 0) + ":" + std::to_string(n) + ":" + std::to_string(iterations);
-    for (int i = 0; i < nctx; ++i) key += ":" + std::to_string(ctxs[i]->serial) + "." + std::to_string(ctxs[i]->opt_side_branches);
+    for (int i = 0; i < nctx; ++i) key += ":" + std::to_string(ctxs[i]->serial) + "." + option_key(ctxs[i]);   // every lane's full option tuple
     auto it = c0->group_graphs.find(key);
     if (it == c0->group_graphs.end()) {
         while ((int)c0->group_events.size() < nctx) {
@@ -3255,6 +3353,8 @@ static int run_single_layer(demon_ctx *c, Layer::Kind kind, float *out, const fl
     if (!L.in.base || !L.out.base || !plan_layer(&scratch, &L))   // (buffer() says why when it refused a size: 2^31-element limit)
         rc = fail(c, DEMON_ERR_HIP, scratch.err.empty() ? std::string("temporary device allocation failed") : scratch.err);
     if (!rc && upload_kernel(&scratch, &L, w)) rc = fail(c, DEMON_ERR_HIP, scratch.err);
+    L.precision = &c->opt_precision;   // (bf16 mode: the shape rule alone decides, the layer has no name)
+    if (!rc && L.bf16_on() && !alloc_bf16(&scratch, &L)) rc = fail(c, DEMON_ERR_HIP, "temporary device allocation failed (bf16 weights)");
     if (!rc && hipMemcpy(L.d_bias, bias, sizeof(float) * cout, hipMemcpyHostToDevice) != hipSuccess) rc = fail(c, DEMON_ERR_HIP, "bias upload failed");
     if (!rc && hipMemcpy(L.in.base, in, sizeof(float) * (size_t)n * cin * h * wd, hipMemcpyHostToDevice) != hipSuccess)
         rc = fail(c, DEMON_ERR_HIP, "input upload failed");

@@ -181,6 +181,15 @@ int conv_tile_bm(int tile);
 int conv_tile_bn(int tile);
 
 void launch_splitk_reduce(const ConvArgs &a, int nclasses, hipStream_t stream);
+
+// ---- the same contraction on the bf16 matrix cores (conv_bf16.hip; option precision = 1) ------------------------------------------------
+// ConvArgs as for launch_conv_mfma except: ktab = the bf16 K table and Kpad = its padding Kb (a multiple of kBf16K); wp unused, the weights
+// are `wb`, bf16 [cls][Kb / 8][Mpad][8] (launch_bf16_repack).  Tiles: enum ConvTile; split-K through conv_splitk_reduce.
+constexpr int kBf16K = 32;   // reduction depth of one K-step
+void launch_conv_bf16(const ConvArgs &a, const void *wb, ConvPlan plan, int nclasses, hipStream_t stream);
+ConvPlan choose_bf16_plan(int Mpad, long pixels, int nclasses, int Kb, long ws_floats);
+void launch_bf16_repack(void *wb, const float *wp, int ncls, int K, int Kb, int Mpad, long cls_w_stride, hipStream_t s);
+
 // demon_profile_full: when set, launch_splitk_reduce records this event on the stream in front of the reduce kernel (and sets the
 // flag), so that a layer's own kernel and the reduce launch that follows it are timed separately
 // compute units the launches of this thread run on: the CU count of the context's mask (demon_set_cu_mask), 0 = the whole device.  Read by the

@@ -22,15 +22,28 @@ def _f32(a, shape=None, name="array"):
     return a
 
 
+PRECISIONS = {"fp32": 0, "bf16": 1}   # option "precision": bf16 operands (fp32 accumulation) on the eligible contraction layers
+
+
+def precision_code(precision):
+    """"fp32" / "bf16" -> the value of option "precision"; anything else raises DemonError (before any HIP call)"""
+    if precision not in PRECISIONS:
+        raise DemonError("precision must be one of %s, not %r" % (", ".join(sorted(PRECISIONS)), precision))
+    return PRECISIONS[precision]
+
+
 class DemonContext:
     created_in_process = 0     # contexts ever created here: the HIP runtime is initialised once this is > 0 (demon_amd.lanes)
     OUTPUT_KEYS = ("predict_flow5", "predict_conf5", "predict_flow2", "predict_conf2", "predict_depth2",
                    "predict_normal2", "predict_rotation", "predict_translation", "predict_scale")
 
-    def __init__(self, device=0, max_batch=1, height=192, width=256, version=1):
-        """version 1: networks_original.py / blocks_original.py; version 2: v2/networks.py / v2/blocks.py"""
+    def __init__(self, device=0, max_batch=1, height=192, width=256, version=1, precision="fp32"):
+        """version 1: networks_original.py / blocks_original.py; version 2: v2/networks.py / v2/blocks.py.
+        precision "bf16": the conv / deconv / dense layers with >= 16 input and >= 8 output channels (but motion_fc2) multiply
+        bf16-rounded operands, accumulating in fp32 (option "precision", include/demon_hip.h)"""
         if version not in (1, 2):
             raise DemonError("version must be 1 (original) or 2 (v2)")
+        prec = precision_code(precision)
         self.lib = _lib.load()
         self.h = ctypes.c_void_p()
         self.version = version
@@ -41,6 +54,12 @@ class DemonContext:
         DemonContext.created_in_process += 1
         self.device, self.max_batch, self.H, self.W = device, max_batch, height, width
         self.h2, self.w2, self.h5, self.w5 = height // 4, width // 4, height // 32, width // 32
+        if prec:
+            try:
+                self.set_option("precision", prec)
+            except DemonError:
+                self.close()
+                raise
 
     @classmethod
     def ops_only(cls, device=0):
@@ -191,6 +210,14 @@ class DemonContext:
         v = ctypes.c_int()
         self._check(self.lib.demon_get_option(self.h, key.encode(), ctypes.byref(v)))
         return int(v.value)
+
+    @property
+    def precision(self):
+        """"fp32" or "bf16" (option "precision")"""
+        return "bf16" if self.get_option("precision") == 1 else "fp32"
+
+    def set_precision(self, precision):
+        self.set_option("precision", precision_code(precision))
 
     def check_guards(self):
         """demon_debug_check_guards (contexts created under DEMON_POISON_GUARD=1): number of canary zones a kernel wrote into"""

@@ -25,6 +25,9 @@ def kernel_tag(name):
     m = re.search(r"conv_mfma_kernel<(\d+), (\d+)", name)
     if m:
         return "conv_mfma<%sx%s>" % m.groups()
+    m = re.search(r"conv_bf16_kernel<(\d+), (\d+)", name)
+    if m:   # option precision = 1 (conv_bf16.hip)
+        return "conv_bf16<%sx%s>" % m.groups()
     m = re.search(r"conv_patch_kernel<(\d+), (\d+), (\d+), (\d+), (\d+), (\d+)", name)
     if m:
         bm, wm, wn, tm, tn, taps = map(int, m.groups())
@@ -108,6 +111,8 @@ def rocprof_kernel_name(tag):
     dims = rest.rstrip(">").split(",")[0].split("x") if rest else []
     if fam == "conv_mfma" and len(dims) == 2:
         return "demon::conv_mfma_kernel<%s, %s, ...>" % tuple(dims)
+    if fam == "conv_bf16" and len(dims) == 2:
+        return "demon::conv_bf16_kernel<%s, %s, ...>" % tuple(dims)
     if fam == "conv_patch" and len(dims) == 2:
         return "demon::conv_patch_kernel<%s, ...> (%sx%s tile, %s taps)" % (dims[0], dims[0], dims[1], rest.rstrip(">").split(",t")[-1])
     if fam == "wino_deconv" and len(dims) == 2:

@@ -28,7 +28,7 @@ import os
 import sys
 import warnings
 
-from .engine import DemonContext
+from .engine import DemonContext, precision_code
 
 # ---- hardware queues ------------------------------------------------------------------------------------------------------------
 # The HIP runtime multiplexes a process's streams onto GPU_MAX_HW_QUEUES hardware queues (default 4), and two busy lanes that share
@@ -99,7 +99,8 @@ def cu_masks(lanes, layout="block", share=1, slots=32, xcds=8):
 class LaneGroup:
     _cache = {}     # mapping_key -> {"lanes", "placeholder_streams", "pairs_per_s"}
 
-    def __init__(self, weights=None, lanes=3, batch=32, height=192, width=256, device=0, version=1, first=None, plan_batch=None, partitions=1):
+    def __init__(self, weights=None, lanes=3, batch=32, height=192, width=256, device=0, version=1, first=None, plan_batch=None, partitions=1,
+                 precision="fp32"):
         """first: an existing context that becomes lane 0 (it already holds its weights, e.g. a rank's context after the RCCL
         broadcast); otherwise lane 0 is created here and takes `weights` (dict tf name -> array).
         partitions = P > 1 (round 6): the compute units are split into P equal shares of every XCD (cu_masks) and lane j runs on share
@@ -109,6 +110,8 @@ class LaneGroup:
             raise ValueError("lanes must be >= 1")
         if partitions < 1 or (partitions > 1 and (32 % partitions or lanes % partitions)):
             raise ValueError("partitions must divide 32 CU slots per XCD and the lane count")
+        precision_code(precision)   # precision: every lane's (a borrowed lane 0 gets its own value back on close())
+        self.precision = precision
         self.batch, self.H, self.W, self.device, self.version = batch, height, width, device, version
         self._owns_first = first is None
         self._plan_batch = plan_batch or batch
@@ -117,6 +120,7 @@ class LaneGroup:
             first.set_weights(weights)
             first.load_tuned_plan(self._plan_batch, lanes=lanes)
         self._first_side = first.get_option("side_branches")     # a borrowed lane 0 goes back the way it came
+        self._first_precision = first.get_option("precision")
         self.ctxs = [first]
         plan = first.get_plan(self._plan_batch)
         for _ in range(lanes - 1):
@@ -136,6 +140,8 @@ class LaneGroup:
                     c.set_plan(self._plan_batch, plan)
             pm = cu_masks(partitions, "block")
             self.set_cu_masks([pm[j % partitions] for j in range(lanes)])
+        for c in self.ctxs:
+            c.set_precision(precision)
         self._side_off = lanes > 1
         if self._side_off:
             for c in self.ctxs:
@@ -155,6 +161,7 @@ class LaneGroup:
                     c.set_cu_mask(None)            # the borrowed context gets the whole chip back
                 self._apply(0, ctxs=[c])           # its placeholder streams go; the borrowed context keeps working
                 c.set_option("side_branches", self._first_side)
+                c.set_option("precision", self._first_precision)
         self.ctxs = []
 
     # ---- the C ABI underneath ------------------------------------------------------------------------------------------------------
@@ -173,8 +180,9 @@ class LaneGroup:
     def mapping_key(self):
         """what a measured (lanes, placeholder streams) winner depends on, as far as this process can tell: the streams other
         libraries hold (torch.distributed / RCCL under a launcher, torch itself) shift the mapping"""
-        return "dev%d_%dx%d_v%d_n%d_l%d_p%d_ws%s_torch%d" % (self.device, self.H, self.W, self.version, self.batch, self._requested, self.partitions,
-                                                             os.environ.get("WORLD_SIZE", "1"), int("torch" in sys.modules))
+        return "dev%d_%dx%d_v%d_n%d_l%d_p%d_ws%s_torch%d%s" % (self.device, self.H, self.W, self.version, self.batch, self._requested, self.partitions,
+                                                               os.environ.get("WORLD_SIZE", "1"), int("torch" in sys.modules),
+                                                               "" if self.precision == "fp32" else "_" + self.precision)
 
     @classmethod
     def _cache_file(cls):

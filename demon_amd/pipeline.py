@@ -48,11 +48,12 @@ class HostBuffers:
 
 
 class Pipeline:
-    def __init__(self, weights, batch=32, height=192, width=256, device=0, version=1, contexts=3, calibrate=False):
+    def __init__(self, weights, batch=32, height=192, width=256, device=0, version=1, contexts=3, calibrate=False, precision="fp32"):
         """contexts = lanes; calibrate=True: create `contexts` lanes, measure 2 .. contexts lanes on zero inputs and keep the best
-        count (LaneGroup.calibrate; at least 2 lanes stay, so that copies still overlap kernels)"""
+        count (LaneGroup.calibrate; at least 2 lanes stay, so that copies still overlap kernels); precision "fp32" / "bf16": every
+        lane's (DemonContext)"""
         self.batch, self.H, self.W = batch, height, width
-        self.lanes = LaneGroup(weights, contexts, batch, height, width, device, version)
+        self.lanes = LaneGroup(weights, contexts, batch, height, width, device, version, precision=precision)
         self.ctxs = self.lanes.ctxs
         self.lane_rates = None
         if calibrate and contexts > 2:

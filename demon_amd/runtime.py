@@ -42,7 +42,8 @@ def get_context(batch_size=1, height=192, width=256, device=None, version=1, ses
     key = (device, batch_size, height, width, version, id(owner) if owner is not None else 0)
     ctx = _contexts.get(key)
     if ctx is None:
-        ctx = DemonContext(device, batch_size, height, width, version)
+        # DEMON_PRECISION=bf16: bf16 operands on the eligible layers (DemonContext(precision=...)), for drivers that cannot pass it
+        ctx = DemonContext(device, batch_size, height, width, version, precision=os.environ.get("DEMON_PRECISION", "fp32"))
         if os.environ.get("DEMON_HIPGRAPH", "1") == "0":
             ctx.set_option("hipgraph", 0)
         ctx.load_tuned_plan(batch_size)   # measured launch plan for this shape, when one is shipped (demon_amd/tuned)

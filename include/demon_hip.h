@@ -94,7 +94,13 @@ int demon_set_weights_blob_device(demon_ctx *ctx, const void *device_blob, int64
  * the intermediate staying in LDS (conv_pair.hip) -- same arithmetic, other summation order;
  * "fused_inputs" 0/1 (default 1): the extra-input assembly of the iterative blocks / the refinement input as one launch each;
  * "tune_lanes" 1..8 (default 1): demon_autotune times every candidate as that many CONCURRENT replays on as many streams
- * ("throughput mode") -- the right cost when several passes are in flight on the GPU (demon_amd/lanes.py) */
+ * ("throughput mode") -- the right cost when several passes are in flight on the GPU (demon_amd/lanes.py);
+ * "precision" 0 = fp32 (default), 1 = bf16 (other values: DEMON_ERR_INVALID): every conv / transposed conv / dense layer with
+ * >= 16 input and >= 8 output channels, except motion_fc2 (fused with motion_fc3 in an fp32 kernel), computes
+ * bias + sum bf16(x) * bf16(w) with round-to-nearest-even operands and fp32 accumulation on the bf16 matrix cores; bias, activation,
+ * stores and every other layer and op stay fp32, activations stay fp32 in memory.  Also applies to demon_op_conv2d /
+ * _deconv4x4s2 / _dense (by the channel rule alone).  Launch plans (demon_autotune, demon_plan_*) keep describing the fp32 path;
+ * the bf16 weights are derived from the packed ones on the first run in that mode. */
 int demon_set_option(demon_ctx *ctx, const char *key, int value);
 int demon_get_option(const demon_ctx *ctx, const char *key, int *value);
 /* Times every applicable kernel variant (im2col / patch-staged, tile shape, split-K) of every layer at batch n on
