@@ -7,6 +7,7 @@ import pytest
 import torch
 
 from conftest import make_inputs, rel_l1
+import exact_ref as X
 import test_bf16_cpu as E
 
 pytestmark = pytest.mark.gpu
@@ -93,12 +94,14 @@ def _operands(shape, seed, n=3):
 @pytest.mark.parametrize("shape", SHAPES)
 def test_every_tile_and_split_is_exact_to_the_bf16_bound(ops_bf16, shape):
     """a bf16 x bf16 product is exact in fp32, so against float64 on the bf16-rounded operands only the fp32 additions err:
-    |got - ref| <= (K + ksplit + 2) 2^-24 (sum |x||w| + |b|) for every element, tile and split-K"""
+    |got - ref| <= (K + ksplit + 2) 2^-24 (sum |x||w| + |b|) for every element, tile and split-K.  On small non-zero integers
+    (+-1, +-2 are bf16 values; tests/exact_ref.py) nothing rounds at all: every tile and split returns the integer result bit for bit"""
     kind, cin, cout, kh, kw, sh, sw = shape[:7]
     padding = shape[9] if len(shape) > 9 else "caffe"
     x, w, b = _operands(shape, 40)
     ref, mag = _ref64(kind, E.bf16_round(x), E.bf16_round(w), b, (sh, sw), padding)
     K = 4 * cin if kind == "deconv" else (cin if kind == "dense" else kh * kw * cin)
+    ex = X.Layer(kind, cin, cout, kh, kw, (sh, sw), shape[7], shape[8], n=3, padding=padding)
     try:
         for t, (bm, bn) in enumerate(TILES):
             if -(-cout // 32) * 32 % bm:
@@ -112,6 +115,9 @@ def test_every_tile_and_split_is_exact_to_the_bf16_bound(ops_bf16, shape):
                 bad = np.abs(got - ref) > bound
                 assert not bad.any(), "tile %d ksplit %d (%s): %d elements off, worst %.3e over the bound" % (
                     t, ks, tag, bad.sum(), (np.abs(got - ref) / np.maximum(bound, 1e-300)).max())
+                ex.saw_rel(tag, ks)
+                ex.check(ops_bf16, ks, expect="conv_bf16<%dx%d>" % (bm, bn))
+        ex.finish()
         # the heuristic plan (no hook) and the activation
         os.environ.pop("DEMON_FORCE_PLAN")
         got = _run(ops_bf16, kind, x, w, b, (sh, sw), lrelu=True, padding=padding)

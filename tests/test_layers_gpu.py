@@ -4,6 +4,7 @@ import numpy as np
 import pytest
 
 from conftest import rel_l1
+import exact_ref as X
 from oracle import ops_ref
 
 pytestmark = pytest.mark.gpu
@@ -45,6 +46,42 @@ def test_conv_shapes_of_the_nets(gpu_ctx, cfg):
     want = _torch_conv(x, w, b, (sh, sw), True)
     assert got.shape == want.shape
     assert rel_l1(got, want) < 1e-5
+    # the heuristic plan at the real shape, per element against the exact integer result (tests/exact_ref.py): the sum above moves
+    # by ~1e-7 when one of these 1.5 M outputs loses a tap
+    ex = X.Layer("conv", cin, cout, kh, kw, (sh, sw), H, W, n=n)
+    ex.saw_rel(gpu_ctx.last_kernel())
+    ex.check(gpu_ctx)
+    ex.finish()
+
+
+# tf.layers.conv2d(padding='same') as the v2 blocks use it: (cin, cout, kh, kw, sh, sw, H, W), two of tests/test_bf16_gpu.SHAPES
+@pytest.mark.parametrize("cfg", [(64, 16, 3, 3, 2, 2, 24, 32), (32, 64, 1, 7, 1, 2, 12, 16)])
+def test_conv_same_padding(gpu_ctx, cfg):
+    """stride 2 on an even size pads less before than after the image: against float64 PyTorch, and per element against the exact
+    integer result"""
+    import torch
+    import torch.nn.functional as F
+    cin, cout, kh, kw, sh, sw, H, W = cfg
+    rng = np.random.default_rng(24)
+    n = 3
+    x = rng.standard_normal((n, cin, H, W)).astype(np.float32)
+    w = (rng.standard_normal((kh, kw, cin, cout)) / np.sqrt(kh * kw * cin)).astype(np.float32)
+    b = rng.standard_normal((cout,)).astype(np.float32)
+    got = gpu_ctx.conv2d(x, w, b, (sh, sw), lrelu=True, padding="same")
+    tag = gpu_ctx.last_kernel()
+    pads = []
+    for size, k, s in ((W, kw, sw), (H, kh, sh)):
+        tot = max((-(-size // s) - 1) * s + k - size, 0)
+        pads += [tot // 2, tot - tot // 2]
+    y = F.conv2d(F.pad(torch.from_numpy(x).double(), pads), torch.from_numpy(np.ascontiguousarray(w.transpose(3, 2, 0, 1))).double(),
+                 torch.from_numpy(b).double(), stride=(sh, sw))
+    want = torch.where(y >= 0, y, 0.1 * y).numpy()
+    assert got.shape == want.shape == (n, cout, -(-H // sh), -(-W // sw))
+    assert rel_l1(got, want) < 1e-5
+    ex = X.Layer("conv", cin, cout, kh, kw, (sh, sw), H, W, n=n, padding="same")
+    ex.saw_rel(tag)
+    ex.check(gpu_ctx)
+    ex.finish()
 
 
 @pytest.mark.parametrize("cfg", [(3, 5, 3, 3, 1, 1, 7, 9), (5, 33, 3, 1, 2, 1, 9, 5), (7, 3, 1, 5, 1, 2, 4, 11), (1, 1, 9, 1, 2, 1, 5, 3)])
@@ -61,6 +98,10 @@ def test_conv_ragged_vs_naive_c(gpu_ctx, cfg):
             want = ops_ref.conv2d_hwio(x, w, b, (sh, sw), (kh // 2, kw // 2), lrelu)
             assert got.shape == want.shape
             assert rel_l1(got, want) < 1e-5
+        ex = X.Layer("conv", cin, cout, kh, kw, (sh, sw), H, W, n=n)
+        ex.saw_rel(gpu_ctx.last_kernel())
+        ex.check(gpu_ctx)
+        ex.finish()
 
 
 def test_conv_is_transpose_detecting(gpu_ctx):
@@ -91,8 +132,13 @@ def test_deconv(gpu_ctx, cfg):
     want = torch.where(y >= 0, y, 0.1 * y).numpy()
     assert got.shape == want.shape == (n, cout, 2 * H, 2 * W)
     assert rel_l1(got, want) < 1e-5
+    tag = gpu_ctx.last_kernel()
     if cin <= 8:
         assert rel_l1(got, ops_ref.deconv4x4s2_crop(x, w, b, True)) < 1e-5
+    ex = X.Layer("deconv", cin, cout, H=H, W=W, n=n)
+    ex.saw_rel(tag)
+    ex.check(gpu_ctx)
+    ex.finish()
 
 
 @pytest.mark.parametrize("cfg", [(6144, 1024), (1024, 128), (128, 7), (37, 5)])
@@ -106,6 +152,10 @@ def test_dense(gpu_ctx, cfg):
         got = gpu_ctx.dense(x, w, b, lrelu=True)
         want = ops_ref.dense(x, w, b, True)
         assert rel_l1(got, want) < 1e-5
+        ex = X.Layer("dense", cin, cout, n=n)
+        ex.saw_rel(gpu_ctx.last_kernel())
+        ex.check(gpu_ctx)
+        ex.finish()
 
 
 def test_nan_propagates_like_the_reference(gpu_ctx):

@@ -1,13 +1,25 @@
 """Every kernel variant the autotuner may pick (im2col / patch-staged, each tile shape, several split-K factors)
 must give the same layer result.  DEMON_FORCE_PLAN is a test hook read by the library at launch time."""
 import os
+import sys
 
 import numpy as np
 import pytest
 
 from conftest import rel_l1
+import exact_ref as X
 
 pytestmark = pytest.mark.gpu
+
+# kernel family prefixes (tests/test_plans_gpu.FAMILY) that got a per-element check against the exact integer result of
+# tests/exact_ref.py in this run; the last test of this file holds it against the families that can run stand-alone
+CHECKED_EXACTLY = set()
+FINISHED = set()   # the tests of this file that closed their exact checks (Layer.finish) at least once
+
+
+def _done(ex):
+    CHECKED_EXACTLY.update(ex.finish())
+    FINISHED.add(sys._getframe(1).f_code.co_name)
 
 # (kind, cin, cout, kh, kw, sh, sw, H, W)
 LAYERS = [
@@ -49,6 +61,7 @@ def test_all_variants_agree(gpu_ctx, layer):
         w = (rng.standard_normal((kh, kw, cin, cout)) / np.sqrt(kh * kw * cin)).astype(np.float32)
     b = rng.standard_normal((cout,)).astype(np.float32)
     want = _ref(kind, x, w, b, (sh, sw))
+    ex = X.Layer(kind, cin, cout, kh, kw, (sh, sw), H, W, n=n)   # integer operands: every plan also against the exact result, per element
     plans = [(3, 0, 0)] + [(0, t, ks) for t in range(8) for ks in (1, 2, 3, 5)] + [(1, t, ks) for t in range(9) for ks in (0, 2, 3, 5)]
     plans += [(4, v, ks) for v in range(18) for ks in (1, 2, 3, 5)]   # register-streaming kernel (applies when Cin % 16 == 0)
     plans += [(5, v, ks) for v in range(22) for ks in (1, 2, 3, 5)]    # fragment-tiled kernel (same requirement)
@@ -58,8 +71,12 @@ def test_all_variants_agree(gpu_ctx, layer):
         for plan in plans:
             os.environ["DEMON_FORCE_PLAN"] = "%d,%d,%d" % plan
             got = gpu_ctx.deconv4x4s2(x, w, b, lrelu=True) if kind == "deconv" else gpu_ctx.conv2d(x, w, b, (sh, sw), lrelu=True)
+            tag = gpu_ctx.last_kernel()
             err = rel_l1(got, want)
             assert err < 1e-5, "plan %s: rel L1 %.3e" % (plan, err)
+            ex.saw_rel(tag, plan[2])
+            ex.check(gpu_ctx, plan[2])   # (tier by the tag: a forced plan that does not fit the layer falls back)
+        _done(ex)
     finally:
         os.environ.pop("DEMON_FORCE_PLAN", None)
 
@@ -138,6 +155,7 @@ def test_minimal_filtering_deconv(gpu_ctx, shape):
     w = (rng.standard_normal((4, 4, cout, cin)) / np.sqrt(4 * cin)).astype(np.float32)
     b = rng.standard_normal((cout,)).astype(np.float32)
     want = _ref("deconv", x, w, b, (2, 2))
+    ex = X.Layer("deconv", cin, cout, H=H, W=W, n=n)
     try:
         os.environ["DEMON_FORCE_PLAN"] = "1,8,0"
         direct = gpu_ctx.deconv4x4s2(x, w, b, lrelu=True)
@@ -159,6 +177,9 @@ def test_minimal_filtering_deconv(gpu_ctx, shape):
                 assert err < 1e-5, "variant %d split %d: rel L1 %.3e" % (v, ks, err)
                 assert rel_l1(got, direct) < 1e-5
                 np.testing.assert_array_equal(got, gpu_ctx.deconv4x4s2(x, w, b, lrelu=True))   # deterministic
+                ex.saw_rel(tag, ks)
+                ex.check(gpu_ctx, ks)   # sums and differences of integers only: bit-exact
+        _done(ex)
     finally:
         os.environ.pop("DEMON_FORCE_PLAN", None)
 
@@ -184,6 +205,7 @@ def test_minimal_filtering_1d(gpu_ctx, layer):
     w = (rng.standard_normal((kh, kw, cin, cout)) / np.sqrt(kh * kw * cin)).astype(np.float32)
     b = rng.standard_normal((cout,)).astype(np.float32)
     want = _ref("conv", x, w, b, (sh, sw))
+    ex = X.Layer("conv", cin, cout, kh, kw, (sh, sw), H, W, n=n)
     ran = 0
     try:
         for v in range(13):
@@ -197,6 +219,10 @@ def test_minimal_filtering_1d(gpu_ctx, layer):
                 err = rel_l1(got, want)
                 assert err < 1e-5, "variant %d split %d (%s): rel L1 %.3e" % (v, ks, tag, err)
                 np.testing.assert_array_equal(got, gpu_ctx.conv2d(x, w, b, (sh, sw), lrelu=True))   # deterministic
+                ex.saw_rel(tag, ks)
+                ex.check(gpu_ctx, ks)   # 3 / 5 taps: bit-exact; 7 / 9 taps: the rounding of the output transform(s) only
+        if ran:
+            _done(ex)
         if (kh == 1 or kh == 3 == kw) and W % (2 * sw):   # filters along x load 8- / 16-byte vectors: rows must be a multiple of 2 / 4 pixels, else the layer
             assert ran == 0, ran            # stays on the direct kernels (checked above all the same: the forced plan falls back)
         else:
@@ -222,6 +248,7 @@ def test_weight_streaming_dense(gpu_ctx, layer):
     b = rng.standard_normal(cout).astype(np.float32)
     want = x.astype(np.float64) @ w.astype(np.float64) + b
     want = np.where(want >= 0, want, 0.1 * want)
+    ex = X.Layer("dense", cin, cout, n=n)
     try:
         for ks in (1, 2, 3, 5, 9, 16, 36, 64):
             os.environ["DEMON_FORCE_PLAN"] = "11,%d,%d" % (ks & 1, ks)   # variant 1 = non-temporal weight loads
@@ -231,6 +258,9 @@ def test_weight_streaming_dense(gpu_ctx, layer):
             err = rel_l1(got, want)
             assert err < 1e-5, "split %d (%s): rel L1 %.3e" % (ks, tag, err)
             np.testing.assert_array_equal(got, gpu_ctx.dense(x, w, b, lrelu=True))
+            ex.saw_rel(tag, ks)
+            ex.check(gpu_ctx, ks, expect="dense_stream<")
+        _done(ex)
         os.environ["DEMON_FORCE_PLAN"] = "11,0,1"
         got = gpu_ctx.dense(x, w, b, lrelu=False)   # no activation
         assert rel_l1(got, x.astype(np.float64) @ w.astype(np.float64) + b) < 1e-5
@@ -254,6 +284,7 @@ def test_first_layer_weights_in_registers(gpu_ctx, layer):
     w = (rng.standard_normal((9, 1, cin, cout)) / np.sqrt(9 * cin)).astype(np.float32)
     b = rng.standard_normal((cout,)).astype(np.float32)
     want = _ref("conv", x, w, b, (2, 1))
+    ex = X.Layer("conv", cin, cout, 9, 1, (2, 1), H, W, n=n)
     try:
         os.environ["DEMON_FORCE_PLAN"] = "12,0,1"
         got = gpu_ctx.conv2d(x, w, b, (2, 1), lrelu=True)
@@ -263,6 +294,9 @@ def test_first_layer_weights_in_registers(gpu_ctx, layer):
         np.testing.assert_array_equal(got, gpu_ctx.conv2d(x, w, b, (2, 1), lrelu=True))
         lin = gpu_ctx.conv2d(x, w, b, (2, 1), lrelu=False)   # without the activation: the same sums
         np.testing.assert_array_equal(np.where(lin >= 0, lin, np.float32(0.1) * lin), got)
+        ex.saw_rel(gpu_ctx.last_kernel(), 1)
+        ex.check(gpu_ctx, 1, expect="conv_thin<")
+        _done(ex)
     finally:
         os.environ.pop("DEMON_FORCE_PLAN", None)
 
@@ -283,6 +317,7 @@ def test_row_conv_out_of_lds(gpu_ctx, layer):
     w = (rng.standard_normal((1, taps, cin, cout)) / np.sqrt(taps * cin)).astype(np.float32)
     b = rng.standard_normal((cout,)).astype(np.float32)
     want = _ref("conv", x, w, b, (1, 2))
+    ex = X.Layer("conv", cin, cout, 1, taps, (1, 2), H, W, n=n)
     try:
         os.environ["DEMON_FORCE_PLAN"] = "13,0,1"
         got = gpu_ctx.conv2d(x, w, b, (1, 2), lrelu=True)
@@ -292,6 +327,9 @@ def test_row_conv_out_of_lds(gpu_ctx, layer):
         np.testing.assert_array_equal(got, gpu_ctx.conv2d(x, w, b, (1, 2), lrelu=True))
         lin = gpu_ctx.conv2d(x, w, b, (1, 2), lrelu=False)
         np.testing.assert_array_equal(np.where(lin >= 0, lin, np.float32(0.1) * lin), got)
+        ex.saw_rel(gpu_ctx.last_kernel(), 1)
+        ex.check(gpu_ctx, 1, expect="conv_row<")
+        _done(ex)
     finally:
         os.environ.pop("DEMON_FORCE_PLAN", None)
 
@@ -315,6 +353,7 @@ def test_minimal_filtering_3x3_rows_stationary(gpu_ctx, layer):
     w = (rng.standard_normal((3, 3, cin, cout)) / np.sqrt(9 * cin)).astype(np.float32)
     b = rng.standard_normal((cout,)).astype(np.float32)
     want = _ref("conv", x, w, b, (1, 1))
+    ex = X.Layer("conv", cin, cout, 3, 3, (1, 1), H, W, n=n)
     ran = 0
     try:
         forms = set()
@@ -329,7 +368,10 @@ def test_minimal_filtering_3x3_rows_stationary(gpu_ctx, layer):
             err = rel_l1(got, want)
             assert err < 1e-5, "variant %d (%s): rel L1 %.3e" % (v, tag, err)
             np.testing.assert_array_equal(got, gpu_ctx.conv2d(x, w, b, (1, 1), lrelu=True))
+            ex.saw_rel(tag, 1)
+            ex.check(gpu_ctx, 1)   # F(2,3) tiles: bit-exact; F(4,3) tiles: the rounding of one output transform
         assert ran >= 1, layer
+        _done(ex)
         if W % 4 == 0 and (cout > 16 or W >= 128):   # (the one-channel-block F(4,3) shapes are 256 pixels wide)
             assert forms == {"wino3rows<t3x3", "wino3rows<f4t3x3"}, forms   # both forms ran
     finally:
@@ -354,6 +396,7 @@ def test_minimal_filtering_3x3_stride2_rows(gpu_ctx, layer):
     w = (rng.standard_normal((3, 3, cin, cout)) / np.sqrt(9 * cin)).astype(np.float32)
     b = rng.standard_normal((cout,)).astype(np.float32)
     want = _ref("conv", x, w, b, (2, 2))
+    ex = X.Layer("conv", cin, cout, 3, 3, (2, 2), H, W, n=n)
     ran = []
     try:
         for v in range(20):
@@ -371,7 +414,10 @@ def test_minimal_filtering_3x3_stride2_rows(gpu_ctx, layer):
             np.testing.assert_array_equal(got, gpu_ctx.conv2d(x, w, b, (2, 2), lrelu=True))
             lin = gpu_ctx.conv2d(x, w, b, (2, 2), lrelu=False)
             np.testing.assert_array_equal(np.where(lin >= 0, lin, np.float32(0.1) * lin), got)
+            ex.saw_rel(tag, 1)
+            ex.check(gpu_ctx, 1, expect="wino3rows<s2t3x3")
         assert ran, layer
+        _done(ex)
         if (cin, cout) == (32, 64):
             assert set(ran) >= {16, 17, 18}, ran
         if (cin, cout) == (64, 128) and W == 64:
@@ -401,6 +447,7 @@ def test_minimal_filtering_four_outputs_per_window(gpu_ctx, layer):
     w = (rng.standard_normal((kh, kw, cin, cout)) / np.sqrt(kh * kw * cin)).astype(np.float32)
     b = rng.standard_normal((cout,)).astype(np.float32)
     want = _ref("conv", x, w, b, (sh, sw))
+    ex = X.Layer("conv", cin, cout, kh, kw, (sh, sw), H, W, n=n)
     ran = walked = 0
     try:
         for v in range(14):     # 9 .. 13: the three-lines-per-wave shapes of round 6 (staging units that do not divide the threads)
@@ -420,7 +467,10 @@ def test_minimal_filtering_four_outputs_per_window(gpu_ctx, layer):
                 else:   # (another template instance: the compiler contracts its epilogue's multiply-adds its own way -- last-bit differences)
                     walked += ",walk" in tag
                     assert rel_l1(got, plain) < 1e-6, tag
+                ex.saw_rel(tag, mode)
+                ex.check(gpu_ctx, mode, expect="wino4<")   # plain, walking and flat launches alike: one output transform per accumulator set
         assert ran >= 1, layer
+        _done(ex)
     finally:
         os.environ.pop("DEMON_FORCE_PLAN", None)
 
@@ -443,6 +493,7 @@ def test_flat_line_order_equals_the_per_image_tiles(gpu_ctx, layer):
     w = (rng.standard_normal((kh, kw, cin, cout)) / np.sqrt(kh * kw * cin)).astype(np.float32)
     b = rng.standard_normal((cout,)).astype(np.float32)
     want = _ref("conv", x, w, b, (sh, sw))
+    ex = X.Layer("conv", cin, cout, kh, kw, (sh, sw), H, W, n=n)   # (every image of the batch distinct: a line taken from the next image shows)
     flat = 0
     try:
         for v in range(14):
@@ -455,17 +506,25 @@ def test_flat_line_order_equals_the_per_image_tiles(gpu_ctx, layer):
             err = rel_l1(got, want)
             assert err < 1e-5, "variant %d (%s): rel L1 %.3e" % (v, tag, err)
             np.testing.assert_array_equal(got, gpu_ctx.conv2d(x, w, b, (sh, sw), lrelu=True))
+            ex.saw_rel(tag, 3)
+            assert ",flat>" in ex.check(gpu_ctx, 3)
             os.environ["DEMON_FORCE_PLAN"] = "16,%d,1" % v
             plain = gpu_ctx.conv2d(x, w, b, (sh, sw), lrelu=True)
             if gpu_ctx.last_kernel() == "wino4<t%d,v%d>" % (max(kh, kw), v):
                 np.testing.assert_array_equal(got, plain)   # same template instance, same sums per output: bit-identical
         if (H, W) in ((12, 16), (12, 32), (6, 8), (6, 16)):
             assert flat >= 1, layer
+        if flat:
+            _done(ex)
     finally:
         os.environ.pop("DEMON_FORCE_PLAN", None)
 
 
-@pytest.mark.parametrize("shape", [(24, 4, 48, 64), (24, 4, 21, 48), (16, 1, 40, 192), (16, 1, 9, 200), (24, 3, 17, 130), (10, 2, 12, 36), (24, 4, 48, 256)])
+# (cin, cout, H, W)
+SMALL_LAYERS = [(24, 4, 48, 64), (24, 4, 21, 48), (16, 1, 40, 192), (16, 1, 9, 200), (24, 3, 17, 130), (10, 2, 12, 36), (24, 4, 48, 256)]
+
+
+@pytest.mark.parametrize("shape", SMALL_LAYERS)
 def test_small_heads_narrow_and_wide_tiles(gpu_ctx, shape):
     """conv_small.hip (plan kind 3): the Cout <= 4 heads.  Round 6 gave it 64-wide tiles for maps whose last 128-wide tile would be at most
     half full (the 48 x 64 heads of every block); both tile widths, widths that are not multiples of 4 (scalar staging path), every
@@ -476,28 +535,38 @@ def test_small_heads_narrow_and_wide_tiles(gpu_ctx, shape):
     w = (rng.standard_normal((3, 3, cin, cout)) / np.sqrt(9 * cin)).astype(np.float32)
     b = rng.standard_normal((cout,)).astype(np.float32)
     want = _ref("conv", x, w, b, (1, 1))
+    ex = X.Layer("conv", cin, cout, 3, 3, (1, 1), H, W, n=3)
     try:
         os.environ["DEMON_FORCE_PLAN"] = "3,0,0"
         got = gpu_ctx.conv2d(x, w, b, (1, 1), lrelu=True)
         assert gpu_ctx.last_kernel().startswith("conv_small"), gpu_ctx.last_kernel()
         assert rel_l1(got, want) < 1e-5
         np.testing.assert_array_equal(got, gpu_ctx.conv2d(x, w, b, (1, 1), lrelu=True))
+        ex.saw_rel(gpu_ctx.last_kernel(), 0)
+        ex.check(gpu_ctx, 0, expect="conv_small")
+        _done(ex)
     finally:
         os.environ.pop("DEMON_FORCE_PLAN", None)
 
 
-@pytest.mark.parametrize("layer", [(64, 64, 3, 1, 48, 64), (64, 64, 1, 3, 48, 64), (128, 128, 3, 1, 24, 32), (128, 128, 1, 3, 24, 32), (256, 256, 3, 1, 12, 16)])
+# (cin, cout, kh, kw, H, W)
+WALK_LAYERS = [(64, 64, 3, 1, 48, 64), (64, 64, 1, 3, 48, 64), (128, 128, 3, 1, 24, 32), (128, 128, 1, 3, 24, 32), (256, 256, 3, 1, 12, 16)]
+WALK_BATCH = 26
+
+
+@pytest.mark.parametrize("layer", WALK_LAYERS)
 def test_tile_walking_workgroups_equal_the_plain_launch(gpu_ctx, layer):
     """conv_wino4.hip, plan field ksplit = 2 (round 6): fewer workgroups than tiles, each walking a whole number of tiles with the next
     tile's first loads issued under the current tile's epilogue.  At a batch where the tiles exceed one round of the chip the walking
     form must really run (kernel tag ",walk"): against PyTorch <= 1e-5, within 1e-6 of the plain launch, deterministic."""
     cin, cout, kh, kw, H, W = layer
     rng = np.random.default_rng(62)
-    n = 26
+    n = WALK_BATCH
     x = rng.standard_normal((n, cin, H, W)).astype(np.float32)
     w = (rng.standard_normal((kh, kw, cin, cout)) / np.sqrt(kh * kw * cin)).astype(np.float32)
     b = rng.standard_normal((cout,)).astype(np.float32)
     want = _ref("conv", x, w, b, (1, 1))
+    ex = X.Layer("conv", cin, cout, kh, kw, (1, 1), H, W, n=n)
     walked = 0
     try:
         for v in range(14):
@@ -506,13 +575,33 @@ def test_tile_walking_workgroups_equal_the_plain_launch(gpu_ctx, layer):
             if not gpu_ctx.last_kernel().startswith("wino4<"):
                 continue
             assert rel_l1(plain, want) < 1e-5, v
+            ex.saw_rel(gpu_ctx.last_kernel(), 1)
+            ex.check(gpu_ctx, 1, expect="wino4<")
             os.environ["DEMON_FORCE_PLAN"] = "16,%d,2" % v
             got = gpu_ctx.conv2d(x, w, b, (1, 1), lrelu=True)
             tag = gpu_ctx.last_kernel()
             assert rel_l1(got, want) < 1e-5 and rel_l1(got, plain) < 1e-6, tag     # (last-bit differences: another template instance, other multiply-add contractions)
             np.testing.assert_array_equal(got, gpu_ctx.conv2d(x, w, b, (1, 1), lrelu=True), err_msg=tag)   # deterministic
             walked += ",walk" in tag
+            ex.saw_rel(tag, 2)
+            assert ex.check(gpu_ctx, 2) == tag
+        _done(ex)
         if H * W >= 24 * 32:   # (the 12 x 16 layer has fewer tiles than the chip has workgroup slots at this batch: nothing to walk, the plain launch runs)
             assert walked >= 2, "no shape ran its tile-walking form at batch %d" % n
     finally:
         os.environ.pop("DEMON_FORCE_PLAN", None)
+
+
+def test_every_standalone_family_was_checked_exactly():
+    """Runs last in this file: the tests above, taken together, must have held every kernel family that can run a layer on its own
+    to the exact integer result (kinds 6 / 7 launch pairs of layers and stay with their bit-for-bit test in test_nets_gpu.py).  On
+    its own, or after a selection of them, there is nothing to judge."""
+    tests = {"test_all_variants_agree", "test_minimal_filtering_deconv", "test_minimal_filtering_1d", "test_weight_streaming_dense", "test_first_layer_weights_in_registers",
+             "test_row_conv_out_of_lds", "test_minimal_filtering_3x3_rows_stationary", "test_minimal_filtering_3x3_stride2_rows", "test_minimal_filtering_four_outputs_per_window",
+             "test_flat_line_order_equals_the_per_image_tiles", "test_small_heads_narrow_and_wide_tiles", "test_tile_walking_workgroups_equal_the_plain_launch"}
+    assert FINISHED <= tests, FINISHED - tests
+    if not CHECKED_EXACTLY or FINISHED != tests:
+        pytest.skip("only %d of the %d tests with exact checks ran before this one" % (len(FINISHED), len(tests)))
+    from test_plans_gpu import FAMILY
+    need = {p for kind, prefixes in FAMILY.items() if kind not in (6, 7) for p in prefixes}
+    assert need <= CHECKED_EXACTLY, "families without an exact check: %s" % sorted(need - CHECKED_EXACTLY)
