@@ -12,6 +12,7 @@ LIB_PATH = os.environ.get("DEMON_HIP_LIB", os.path.join(HERE, "libdemon_hip.so")
 c_float_p = ctypes.POINTER(ctypes.c_float)
 c_int_p = ctypes.POINTER(ctypes.c_int)
 c_int64_p = ctypes.POINTER(ctypes.c_int64)
+c_uint8_p = ctypes.POINTER(ctypes.c_uint8)
 
 
 class DemonOutputs(ctypes.Structure):
@@ -89,6 +90,10 @@ SIGNATURES = {
     "demon_download_outputs": (_I, [_P, _I, ctypes.POINTER(DemonOutputs), c_float_p]),
     "demon_download_normal0": (_I, [_P, _I, c_float_p]),
     "demon_upload_inputs_async": (_I, [_P, _I, c_float_p, c_float_p]),
+    "demon_ingest_configure": (_I, [_P, _I, _I]),
+    "demon_upload_images_u8": (_I, [_P, _I, c_uint8_p, c_uint8_p]),
+    "demon_upload_images_u8_async": (_I, [_P, _I, c_uint8_p, c_uint8_p]),
+    "demon_op_prepare_inputs_u8": (_I, [_P, c_float_p, c_float_p, c_uint8_p, c_uint8_p, _I, _I, _I, _I, _I]),
     "demon_download_outputs_async": (_I, [_P, _I, ctypes.POINTER(DemonOutputs), c_float_p]),
     "demon_host_register": (_I, [ctypes.c_void_p, ctypes.c_int64]),
     "demon_host_unregister": (_I, [ctypes.c_void_p]),
@@ -107,6 +112,7 @@ SIGNATURES = {
     "demon_op_deconv4x4s2": (_I, [_P, c_float_p, c_float_p, c_float_p, c_float_p] + [_I] * 6),
     "demon_op_dense": (_I, [_P, c_float_p, c_float_p, c_float_p, c_float_p] + [_I] * 4),
     "demon_bench_layer": (_I, [_P] + [_I] * 13 + [c_float_p, ctypes.POINTER(ctypes.c_double)]),
+    "demon_bench_ingest": (_I, [_P, _I, _I, _I, c_float_p, c_float_p]),
     "demon_last_kernel": (_I, [ctypes.c_char_p, _I]),
     "demon_debug_check_guards": (_I, [_P, c_int_p]),
 }

@@ -213,6 +213,11 @@ struct demon_ctx {
     float *d_zero = nullptr;  // shared zero page of the conv_stream layers
     std::vector<std::pair<Layer *, Layer *>> chain_pairs;  // stride-1 k x 1 / 1 x k pairs that can run as one chained launch
     std::vector<std::pair<Layer *, Layer *>> fused_pairs;  // pairs conv_pair.hip runs as one launch unless the plan of the k x 1 layer is kind 12
+    // demon_ingest_configure: uint8 staging for max_batch pairs of ingest_h x ingest_w images and the two index tables (ingest.hip);
+    // nothing of it exists until that call
+    uint8_t *d_u8[2] = {nullptr, nullptr};
+    int *d_rowtab = nullptr, *d_coltab = nullptr;
+    int ingest_h = 0, ingest_w = 0;
 };
 
 namespace {
@@ -250,6 +255,18 @@ float *dev_alloc(demon_ctx *c, size_t bytes)
     if (hipMalloc(&p, bytes) != hipSuccess) return nullptr;
     c->allocations.push_back(p);
     return (float *)p;
+}
+
+// gives one dev_alloc allocation back (demon_ingest_configure replaces its staging): the entry leaves c->allocations and the guard list
+void dev_free(demon_ctx *c, void *payload)
+{
+    if (!payload) return;
+    void *raw = c->guard_bytes ? (void *)((char *)payload - c->guard_bytes) : payload;
+    for (size_t i = 0; i < c->guarded.size(); ++i)
+        if (c->guarded[i].first == (char *)raw) { c->guarded.erase(c->guarded.begin() + i); break; }
+    for (size_t i = 0; i < c->allocations.size(); ++i)
+        if (c->allocations[i] == raw) { c->allocations.erase(c->allocations.begin() + i); break; }
+    hipFree(raw);
 }
 
 // number of guard zones that no longer hold the canary (0 = nothing wrote outside its tensor); `where` names the first one
@@ -2731,6 +2748,109 @@ int demon_upload_inputs_async(demon_ctx *c, int n, const float *image_pair, cons
     return h2d(c, c->image2_2, image2_2, n);
 }
 
+// ---- uint8 image pairs (ingest.hip; replaces prepare_input_data, examples/example.py:15-42) ------------------------------------------
+int demon_ingest_configure(demon_ctx *c, int src_h, int src_w)
+{
+    if (!c) return DEMON_ERR_INVALID;
+    if (!c->max_batch) return fail(c, DEMON_ERR_INVALID, "demon_ingest_configure needs a network context");
+    if (!ingest_shape_ok(c->max_batch, src_h, src_w, c->H, c->W)) return fail(c, DEMON_ERR_INVALID, "source size out of range (>= 1 x 1, at most 2^31 bytes per image)");
+    hipSetDevice(c->device);
+    if (c->stream) HIP_TRY(c, hipStreamSynchronize(c->stream));   // nothing may be in flight: a pending ingest launch reads what is freed here
+    if (c->d_u8[0] && c->ingest_h == src_h && c->ingest_w == src_w) return DEMON_OK;
+    dev_free(c, c->d_u8[0]); dev_free(c, c->d_u8[1]); dev_free(c, c->d_rowtab); dev_free(c, c->d_coltab);
+    c->d_u8[0] = c->d_u8[1] = nullptr; c->d_rowtab = c->d_coltab = nullptr;
+    c->ingest_h = c->ingest_w = 0;
+    const size_t bytes = (size_t)c->max_batch * src_h * src_w * 3;
+    uint8_t *u0 = (uint8_t *)dev_alloc(c, bytes), *u1 = (uint8_t *)dev_alloc(c, bytes);
+    int *rt = (int *)dev_alloc(c, sizeof(int) * c->H), *ct = (int *)dev_alloc(c, sizeof(int) * c->W);
+    if (!u0 || !u1 || !rt || !ct) {
+        dev_free(c, u0); dev_free(c, u1); dev_free(c, rt); dev_free(c, ct);
+        return fail(c, DEMON_ERR_HIP, "device allocation failed (uint8 staging)");
+    }
+    c->d_u8[0] = u0; c->d_u8[1] = u1; c->d_rowtab = rt; c->d_coltab = ct;
+    std::vector<int> tab(c->H > c->W ? c->H : c->W);
+    ingest_index_table(src_h, c->H, tab.data());
+    HIP_TRY(c, hipMemcpy(rt, tab.data(), sizeof(int) * c->H, hipMemcpyHostToDevice));
+    ingest_index_table(src_w, c->W, tab.data());
+    HIP_TRY(c, hipMemcpy(ct, tab.data(), sizeof(int) * c->W, hipMemcpyHostToDevice));
+    c->ingest_h = src_h; c->ingest_w = src_w;   // (last: a failed upload leaves the context unconfigured)
+    return DEMON_OK;
+}
+
+// the ingest launch over the first n staged pairs, into the context's resident inputs
+static void enqueue_ingest(demon_ctx *c, int n)
+{
+    IngestArgs a{};
+    a.img1 = c->d_u8[0]; a.img2 = c->d_u8[1]; a.rowtab = c->d_rowtab; a.coltab = c->d_coltab;
+    a.pair = c->image_pair.ptr(); a.img22 = c->image2_2.ptr();
+    a.pair_n_stride = c->image_pair.n_stride(); a.img22_n_stride = c->image2_2.n_stride();
+    a.N = n; a.src_h = c->ingest_h; a.src_w = c->ingest_w; a.H = c->H; a.W = c->W;
+    launch_ingest(a, c->stream);
+}
+
+static int upload_images_u8(demon_ctx *c, int n, const uint8_t *image1, const uint8_t *image2)
+{
+    int r = check_batch(c, n);
+    if (r) return r;
+    if (!c->ingest_h) return fail(c, DEMON_ERR_NOT_READY, "no uint8 staging: call demon_ingest_configure first");
+    if (!image1 || !image2) return fail(c, DEMON_ERR_INVALID, "null input pointer");
+    hipSetDevice(c->device);
+    const size_t bytes = (size_t)n * c->ingest_h * c->ingest_w * 3;
+    HIP_TRY(c, hipMemcpyAsync(c->d_u8[0], image1, bytes, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(c->d_u8[1], image2, bytes, hipMemcpyHostToDevice, c->stream));
+    enqueue_ingest(c, n);
+    HIP_TRY(c, hipGetLastError());
+    return DEMON_OK;
+}
+
+// tools/ingest_bench.py: per launch, alternating, the ingest kernel over the staged pairs and ONE device-to-device hipMemcpyAsync of as
+// many bytes as the kernel writes (image_pair + image2_2 of n pairs), each between two hip events on the context's stream
+int demon_bench_ingest(demon_ctx *c, int n, int warmup, int iters, float *kernel_ms, float *copy_ms)
+{
+    if (!c) return DEMON_ERR_INVALID;
+    if (n < 1 || n > c->max_batch || warmup < 0 || iters < 1 || !kernel_ms || !copy_ms) return fail(c, DEMON_ERR_INVALID, "bad argument");
+    if (!c->stream) return fail(c, DEMON_ERR_NOT_READY, kNoStream);
+    if (!c->ingest_h) return fail(c, DEMON_ERR_NOT_READY, "no uint8 staging: call demon_ingest_configure first");
+    hipSetDevice(c->device);
+    TmpDev tmp;
+    const size_t out_floats = (size_t)n * (6 * c->H * c->W + 3 * (c->H / 4) * (c->W / 4));
+    float *from = tmp.alloc(out_floats), *to = tmp.alloc(out_floats);
+    if (!from || !to) return fail(c, DEMON_ERR_HIP, "temporary device allocation failed");
+    HIP_TRY(c, hipMemsetAsync(from, 0, sizeof(float) * out_floats, c->stream));
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) { if (e0) hipEventDestroy(e0); return fail(c, DEMON_ERR_HIP, "hipEventCreate failed"); }
+    int rc = DEMON_OK;
+    for (int i = 0; i < warmup + iters && rc == DEMON_OK; ++i)
+        for (int leg = 0; leg < 2 && rc == DEMON_OK; ++leg) {
+            hipError_t e = hipEventRecord(e0, c->stream);
+            if (leg == 0) enqueue_ingest(c, n);
+            else if (e == hipSuccess) e = hipMemcpyAsync(to, from, sizeof(float) * out_floats, hipMemcpyDeviceToDevice, c->stream);
+            if (e == hipSuccess) e = hipGetLastError();
+            if (e == hipSuccess) e = hipEventRecord(e1, c->stream);
+            if (e == hipSuccess) e = hipEventSynchronize(e1);
+            float ms = 0.0f;
+            if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
+            if (e != hipSuccess) rc = fail(c, DEMON_ERR_HIP, std::string("demon_bench_ingest: ") + hipGetErrorString(e));
+            else if (i >= warmup) (leg ? copy_ms : kernel_ms)[i - warmup] = ms;
+        }
+    hipEventDestroy(e0);
+    hipEventDestroy(e1);
+    return rc;
+}
+
+int demon_upload_images_u8(demon_ctx *c, int n, const uint8_t *image1, const uint8_t *image2)
+{
+    int r = upload_images_u8(c, n, image1, image2);
+    if (r) return r;
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return DEMON_OK;
+}
+
+int demon_upload_images_u8_async(demon_ctx *c, int n, const uint8_t *image1, const uint8_t *image2)
+{
+    return upload_images_u8(c, n, image1, image2);
+}
+
 int demon_download_outputs_async(demon_ctx *c, int n, const demon_outputs *o, float *depth0)
 {
     if (!c || n < 1 || n > c->max_batch) return fail(c, DEMON_ERR_INVALID, "bad batch");
@@ -3218,6 +3338,32 @@ int demon_op_depth_to_flow(demon_ctx *c, float *out, const float *depth, const f
     if (!d_depth || !d_k || !d_r || !d_t || !d_out) return fail(c, DEMON_ERR_HIP, "temporary device allocation failed");
     launch_depth_to_flow(d_out, d_depth, hw, d_k, d_r, d_t, n, h, w, 2 * hw, inverse_depth, normalize_flow, gate, c->stream);
     OP_FINISH(c, d_out, out, 2 * n * hw);
+}
+
+int demon_op_prepare_inputs_u8(demon_ctx *c, float *image_pair, float *image2_2, const uint8_t *image1, const uint8_t *image2, int n,
+                               int src_h, int src_w, int H, int W)
+{
+    OP_PROLOGUE(c);
+    if (!image_pair || !image2_2 || !image1 || !image2 || !ingest_shape_ok(n, src_h, src_w, H, W) || (size_t)n * 6 * H * W >= (1ul << 31))
+        return fail(c, DEMON_ERR_INVALID, "bad argument (H, W multiples of 32; source >= 1 x 1)");
+    const size_t bytes = (size_t)n * src_h * src_w * 3, words = (bytes + 3) / 4, hw = (size_t)H * W;
+    std::vector<int> rt(H), ct(W);
+    ingest_index_table(src_h, H, rt.data());
+    ingest_index_table(src_w, W, ct.data());
+    float *d_1 = tmp.alloc(words), *d_2 = tmp.alloc(words), *d_rt = tmp.upload((const float *)rt.data(), H), *d_ct = tmp.upload((const float *)ct.data(), W),
+          *d_pair = tmp.alloc(6 * n * hw), *d_22 = tmp.alloc(3 * n * hw / 16);
+    if (!d_1 || !d_2 || !d_rt || !d_ct || !d_pair || !d_22) return fail(c, DEMON_ERR_HIP, "temporary device allocation failed");
+    HIP_TRY(c, hipMemcpy(d_1, image1, bytes, hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemcpy(d_2, image2, bytes, hipMemcpyHostToDevice));
+    IngestArgs a{};
+    a.img1 = (const uint8_t *)d_1; a.img2 = (const uint8_t *)d_2; a.rowtab = (const int *)d_rt; a.coltab = (const int *)d_ct;
+    a.pair = d_pair; a.img22 = d_22; a.pair_n_stride = 6 * hw; a.img22_n_stride = 3 * hw / 16;
+    a.N = n; a.src_h = src_h; a.src_w = src_w; a.H = H; a.W = W;
+    launch_ingest(a, c->stream);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, hipMemcpy(image2_2, d_22, sizeof(float) * 3 * n * hw / 16, hipMemcpyDeviceToHost));
+    OP_FINISH(c, d_pair, image_pair, 6 * n * hw);
 }
 
 int demon_op_flow_to_depth(demon_ctx *c, float *out, const float *flow, const float *intrinsics, const float *rotation,

@@ -475,6 +475,19 @@ void launch_conv_small(const SmallConvArgs &a, int N, hipStream_t s);
 void launch_motion_tail(const float *x, const float *w2, const float *b2, const float *w3, const float *b3, float *motion,
                         float *rot, float *trans, float *scale, int N, int K2, int M2pad, int M3pad, hipStream_t s);
 
+// ---- uint8 image pairs -> image_pair / image2_2 (ingest.hip): NEAREST resize, u8 / 255 - 0.5, planar pack, one launch -------------------
+struct IngestArgs {
+    const uint8_t *img1, *img2;   // staged batches [N][src_h][src_w][3]
+    const int *rowtab, *coltab;   // source row of output row y [H], source column of output column x [W] (ingest_index_table)
+    float *pair, *img22;          // [N][6][H][W], [N][3][H/4][W/4]
+    long pair_n_stride, img22_n_stride;
+    int N, src_h, src_w, H, W;
+    int full_blocks;              // workgroups of the full-size planes per image (set by the launcher)
+};
+void ingest_index_table(int src, int dst, int *idx);   // Pillow's NEAREST rule (a running double-precision sum)
+bool ingest_shape_ok(int n, int src_h, int src_w, int H, int W);
+void launch_ingest(IngestArgs a, hipStream_t stream);
+
 // ---- op launchers (ops.hip) --------------------------------------------------------------------
 void launch_depth_to_flow(float *out, const float *depth, long depth_n_stride, const float *intrinsics,
                           const float *rotation, const float *translation, int N, int H, int W,

@@ -4,7 +4,7 @@ import ctypes
 import numpy as np
 
 from . import _lib
-from ._lib import DemonOutputs, LaunchRecord, c_float_p, c_int64_p
+from ._lib import DemonOutputs, LaunchRecord, c_float_p, c_int64_p, c_uint8_p
 
 
 class DemonError(ValueError):
@@ -20,6 +20,24 @@ def _f32(a, shape=None, name="array"):
     if shape is not None and tuple(a.shape) != tuple(shape):
         raise DemonError("%s has shape %s, expected %s" % (name, tuple(a.shape), tuple(shape)))
     return a
+
+
+def _u8p(a):
+    return a.ctypes.data_as(c_uint8_p)
+
+
+def _u8_pair(image1_u8, image2_u8):
+    """the two uint8 [n,h,w,3] C-contiguous arrays of the ingest entry points, checked (nothing is converted or copied)"""
+    for name, a in (("image1_u8", image1_u8), ("image2_u8", image2_u8)):
+        if not isinstance(a, np.ndarray) or a.dtype != np.uint8:
+            raise DemonError("%s must be a uint8 numpy array" % name)
+        if a.ndim != 4 or a.shape[3] != 3 or a.shape[0] < 1 or a.shape[1] < 1 or a.shape[2] < 1:
+            raise DemonError("%s has shape %s, expected [n,h,w,3]" % (name, tuple(a.shape)))
+        if not a.flags["C_CONTIGUOUS"]:
+            raise DemonError("%s must be C-contiguous (row strides are not supported)" % name)
+    if image1_u8.shape != image2_u8.shape:
+        raise DemonError("image1_u8 %s and image2_u8 %s differ in shape" % (tuple(image1_u8.shape), tuple(image2_u8.shape)))
+    return image1_u8, image2_u8
 
 
 PRECISIONS = {"fp32": 0, "bf16": 1}   # option "precision": bf16 operands (fp32 accumulation) on the eligible contraction layers
@@ -297,6 +315,36 @@ class DemonContext:
         self._check(self.lib.demon_upload_inputs(self.h, n, _fp(image_pair), _fp(image2_2)))
         return n
 
+    def configure_ingest(self, src_h, src_w):
+        """demon_ingest_configure: uint8 staging for max_batch pairs of src_h x src_w images and the index tables of the NEAREST
+        resize to the context's size.  Nothing may be in flight; another size replaces the staging."""
+        self._check(self.lib.demon_ingest_configure(self.h, int(src_h), int(src_w)))
+        self._ingest_size = (int(src_h), int(src_w))
+
+    def upload_images(self, image1_u8, image2_u8):
+        """uint8 [n,h,w,3] RGB images -> the resident inputs, resized (Pillow's NEAREST rule), normalised to [-0.5, 0.5] and packed by
+        one kernel: what preprocess.prepare_input_arrays computes, bit for bit.  Configures the staging on first use and when the
+        source size changes (that step waits for the stream)."""
+        a1, a2 = _u8_pair(image1_u8, image2_u8)
+        n = int(a1.shape[0])
+        if getattr(self, "_ingest_size", None) != tuple(a1.shape[1:3]):
+            self.configure_ingest(a1.shape[1], a1.shape[2])
+        self._check(self.lib.demon_upload_images_u8(self.h, n, _u8p(a1), _u8p(a2)))
+        return n
+
+    def prepare_inputs(self, image1_u8, image2_u8, height=192, width=256):
+        """demon_op_prepare_inputs_u8 (works on ops_only contexts): (image_pair [n,6,H,W], image2_2 [n,3,H/4,W/4]) from uint8
+        [n,h,w,3] images, on the GPU"""
+        a1, a2 = _u8_pair(image1_u8, image2_u8)
+        n, h, w = (int(v) for v in a1.shape[:3])
+        height, width = int(height), int(width)
+        if height < 32 or width < 32 or height % 32 or width % 32:
+            raise DemonError("height and width must be positive multiples of 32")
+        pair = np.empty((n, 6, height, width), np.float32)
+        img22 = np.empty((n, 3, height // 4, width // 4), np.float32)
+        self._check(self.lib.demon_op_prepare_inputs_u8(self.h, _fp(pair), _fp(img22), _u8p(a1), _u8p(a2), n, h, w, height, width))
+        return pair, img22
+
     def run_full(self, n, iterations=3):
         self._check(self.lib.demon_run_full(self.h, n, iterations))
 
@@ -471,6 +519,13 @@ class DemonContext:
         buf = ctypes.create_string_buffer(64)
         self.lib.demon_last_kernel(buf, 64)
         return buf.value.decode()
+
+    def bench_ingest(self, n, warmup=5, iters=20):
+        """demon_bench_ingest (after configure_ingest): ([ms] of the ingest kernel over n staged pairs, [ms] of a device-to-device
+        copy of the bytes it writes), `iters` hip-event timings each, alternating; overwrites the resident inputs"""
+        k, c = np.zeros(iters, np.float32), np.zeros(iters, np.float32)
+        self._check(self.lib.demon_bench_ingest(self.h, int(n), int(warmup), int(iters), _fp(k), _fp(c)))
+        return k.tolist(), c.tolist()
 
     def bench_layer(self, kind, n, cin, h, w, cout, kh=1, kw=1, sh=1, sw=1, tile=-1, ksplit=0, iters=20):
         """kind: 'conv' | 'deconv' | 'dense'.  Returns (avg_ms, TFLOP/s)."""

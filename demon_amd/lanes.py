@@ -319,6 +319,11 @@ class LaneGroup:
         """batches: one (image_pair, image2_2) per lane; they stay resident in the lanes' input buffers"""
         return [c.upload_inputs(*b) for c, b in zip(self.ctxs, batches)]
 
+    def upload_images(self, batches):
+        """batches: one (image1_u8, image2_u8) per lane, uint8 [n,h,w,3]; resized, normalised and packed on the GPU into the lanes'
+        resident input buffers (DemonContext.upload_images)"""
+        return [c.upload_images(*b) for c, b in zip(self.ctxs, batches)]
+
     def set_cu_masks(self, masks):
         """demon_set_cu_mask on every lane (masks: one list of 32-bit words per lane, cu_masks(); None / []: every CU again).  Lanes
         on disjoint masks do not compete for compute units wherever the runtime puts their streams."""

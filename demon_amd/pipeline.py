@@ -13,7 +13,7 @@ import time
 
 import numpy as np
 
-from .engine import DemonContext, DemonError, DemonOutputs, _fp
+from .engine import DemonContext, DemonError, DemonOutputs, _fp, _u8p, _u8_pair
 from .lanes import LaneGroup
 
 
@@ -31,14 +31,22 @@ class _Pinned:
 
 
 class HostBuffers:
-    """Page-locked host arrays for B pairs: `image_pair`, `image2_2` (inputs, filled by the caller) and `out[key]` (outputs)."""
+    """Page-locked host arrays for B pairs: `image_pair`, `image2_2` (inputs, filled by the caller) and `out[key]` (outputs).
+    With source_size=(h, w) the inputs are `image1_u8`, `image2_u8` [B,h,w,3] uint8 instead and the GPU prepares them."""
 
-    def __init__(self, lib, shapes, B, H, W):
+    def __init__(self, lib, shapes, B, H, W, source_size=None):
         self.B = B
-        self.image_pair = np.zeros((B, 6, H, W), np.float32)
-        self.image2_2 = np.zeros((B, 3, H // 4, W // 4), np.float32)
+        self.source_size = None if source_size is None else (int(source_size[0]), int(source_size[1]))
+        if self.source_size is None:
+            self.image_pair = np.zeros((B, 6, H, W), np.float32)
+            self.image2_2 = np.zeros((B, 3, H // 4, W // 4), np.float32)
+            inputs = [self.image_pair, self.image2_2]
+        else:
+            self.image1_u8 = np.zeros((B,) + self.source_size + (3,), np.uint8)
+            self.image2_u8 = np.zeros((B,) + self.source_size + (3,), np.uint8)
+            inputs = [self.image1_u8, self.image2_u8]
         self.out = {k: np.zeros((B,) + s, np.float32) for k, s in shapes.items()}
-        self._pins = [_Pinned(lib, a) for a in [self.image_pair, self.image2_2] + list(self.out.values())]
+        self._pins = [_Pinned(lib, a) for a in inputs + list(self.out.values())]
         self.pinned = all(p.ok for p in self._pins)
 
     def release(self):
@@ -72,21 +80,31 @@ class Pipeline:
         self.lanes.close()
         self.ctxs = []
 
-    def buffers(self, B):
-        """page-locked input / output arrays for B pairs (B a multiple of the batch size); release() them when done"""
+    def buffers(self, B, source_size=None):
+        """page-locked input / output arrays for B pairs (B a multiple of the batch size); release() them when done.
+        source_size=(h, w): uint8 inputs `image1_u8` / `image2_u8` [B,h,w,3] instead of the float ones (a quarter of the bytes over
+        PCIe at the context's size; resized, normalised and packed by the GPU: DemonContext.upload_images)"""
         if B % self.batch:
             raise DemonError("B must be a multiple of the batch size %d" % self.batch)
-        return HostBuffers(self.ctxs[0].lib, self.shapes, B, self.H, self.W)
+        return HostBuffers(self.ctxs[0].lib, self.shapes, B, self.H, self.W, source_size)
 
     def run_buffers(self, hb, iterations=3):
         """every pair of `hb` through the pipeline: hb.image_pair / hb.image2_2 -> hb.out[...]; returns when everything has landed"""
         n, lib = self.batch, self.ctxs[0].lib
+        u8 = getattr(hb, "source_size", None)
+        if u8 is not None:
+            for c in self.ctxs[:hb.B // n]:   # (allocates and synchronises: before anything is enqueued, and only on a change of size)
+                if getattr(c, "_ingest_size", None) != u8:
+                    c.configure_ingest(*u8)
         for i in range(hb.B // n):
             c = self.ctxs[i % len(self.ctxs)]
             if i >= len(self.ctxs):
                 c.synchronize()          # its previous batch (inputs consumed, outputs written)
             sl = slice(i * n, (i + 1) * n)
-            c._check(lib.demon_upload_inputs_async(c.h, n, _fp(hb.image_pair[sl]), _fp(hb.image2_2[sl])))
+            if u8 is not None:
+                c._check(lib.demon_upload_images_u8_async(c.h, n, _u8p(hb.image1_u8[sl]), _u8p(hb.image2_u8[sl])))
+            else:
+                c._check(lib.demon_upload_inputs_async(c.h, n, _fp(hb.image_pair[sl]), _fp(hb.image2_2[sl])))
             c.run_full(n, iterations)
             o = DemonOutputs(**{k: _fp(hb.out[k][sl]) for k in DemonContext.OUTPUT_KEYS})
             c._check(lib.demon_download_outputs_async(c.h, n, ctypes.byref(o), _fp(hb.out["predict_depth0"][sl])))
@@ -114,10 +132,29 @@ class Pipeline:
         if B % n or image_pair.shape[1:] != (6, self.H, self.W) or image2_2.shape != (B, 3, self.H // 4, self.W // 4):
             raise DemonError("inputs must be [k*batch,6,H,W] and [k*batch,3,H/4,W/4]")
         hb = HostBuffers.__new__(HostBuffers)
+        hb.source_size = None
         hb.B, hb.image_pair, hb.image2_2 = B, image_pair, image2_2
         hb.out = {k: np.empty((B,) + s, np.float32) for k, s in self.shapes.items()}
         lib = self.ctxs[0].lib
         hb._pins = [_Pinned(lib, a) for a in [image_pair, image2_2] + list(hb.out.values())]
+        hb.pinned = all(p.ok for p in hb._pins)
+        try:
+            return self.run_buffers(hb, iterations)
+        finally:
+            hb.release()
+
+    def run_images(self, image1_u8, image2_u8, iterations=3):
+        """image1_u8, image2_u8: uint8 [B,h,w,3] host arrays, B a multiple of the batch size: run() for images as a camera or a
+        decoder delivers them (resize, normalisation and packing happen on the GPU).  Page-locks the arrays for the call only."""
+        a1, a2 = _u8_pair(image1_u8, image2_u8)
+        B = a1.shape[0]
+        if B % self.batch:
+            raise DemonError("the number of pairs must be a multiple of the batch size %d" % self.batch)
+        hb = HostBuffers.__new__(HostBuffers)
+        hb.B, hb.image1_u8, hb.image2_u8, hb.source_size = B, a1, a2, (int(a1.shape[1]), int(a1.shape[2]))
+        hb.out = {k: np.empty((B,) + s, np.float32) for k, s in self.shapes.items()}
+        lib = self.ctxs[0].lib
+        hb._pins = [_Pinned(lib, a) for a in [a1, a2] + list(hb.out.values())]
         hb.pinned = all(p.ok for p in hb._pins)
         try:
             return self.run_buffers(hb, iterations)

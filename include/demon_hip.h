@@ -9,7 +9,8 @@
  * Conventions
  *   - plain pointers and sizes only; no C++ / torch types; no exceptions cross the ABI
  *   - every function returns 0 on success or a negative demon_status; text via demon_last_error()
- *   - all tensors are float32, NCHW ("channels_first"), contiguous; the Python shim converts NHWC
+ *   - all tensors are float32, NCHW ("channels_first"), contiguous; the Python shim converts NHWC.  The one exception: the
+ *     uint8 images of demon_upload_images_u8* / demon_op_prepare_inputs_u8, [n, src_h, src_w, 3] RGB, channels last, contiguous
  *   - "host" pointers are caller-owned host memory; the context owns all device memory
  *   - a context is bound to one device and one HIP stream and is NOT thread safe
  *   - no device allocation happens inside any run call (hipGraph-capture safe)
@@ -225,6 +226,25 @@ int demon_upload_inputs_async(demon_ctx *ctx, int n, const float *image_pair, co
 int demon_download_outputs_async(demon_ctx *ctx, int n, const demon_outputs *out, float *predict_depth0);
 int demon_host_register(void *ptr, int64_t bytes);
 int demon_host_unregister(void *ptr);
+/* uint8 image pairs straight into the resident inputs: replaces prepare_input_data (examples/example.py:15-42), which resizes, converts
+ * and packs ONE pair on the host with PIL and numpy.  image1 / image2: uint8 [n, src_h, src_w, 3] (RGB, channels last, contiguous).
+ * One kernel launch resizes both to H x W by Pillow's NEAREST rule (the filter of the reference's pinned Pillow; per axis the source
+ * index of output sample x is the truncated double-precision running sum a0 / 2 + a0 + .. + a0, a0 = src / dst -- identity when the
+ * sizes match), makes the quarter-size second image by NEAREST from the RESIZED one (row 4 y + 2, column 4 x + 2), computes
+ * (float)v / 255.0f - 0.5f in IEEE float32 and writes image_pair [n,6,H,W] = [R1 G1 B1 R2 G2 B2] and image2_2 [n,3,H/4,W/4]: bit for
+ * bit what the reference function returns for channels_first.  Bicubic (Pillow >= 7's default), grayscale / alpha and row strides
+ * are not offered.
+ *   demon_ingest_configure       : (network contexts; examples/example.py:15-42) allocates the uint8 staging for max_batch pairs of
+ *                                  src_h x src_w images and uploads the two index tables.  Nothing may be in flight.  Another size
+ *                                  replaces staging and tables.  The only call of the three that allocates or synchronises.
+ *   demon_upload_images_u8       : (examples/example.py:15-42) host -> staging, then the ingest kernel on the context's stream; waits,
+ *                                  like demon_upload_inputs.  DEMON_ERR_NOT_READY without demon_ingest_configure or without streams.
+ *   demon_upload_images_u8_async : (examples/example.py:15-42) the same, enqueued only; page-locked host memory, like
+ *                                  demon_upload_inputs_async.
+ * Afterwards demon_run_full / demon_run_bootstrap work as after demon_upload_inputs (same input buffers: cached graphs stay valid). */
+int demon_ingest_configure(demon_ctx *ctx, int src_h, int src_w);
+int demon_upload_images_u8(demon_ctx *ctx, int n, const uint8_t *image1, const uint8_t *image2);
+int demon_upload_images_u8_async(demon_ctx *ctx, int n, const uint8_t *image1, const uint8_t *image2);
 /* v2 contexts only: predict_normal0 [n,3,H,W] of the last refinement run (v2/networks.py:223-226; v2/blocks.py:560-562). */
 int demon_download_normal0(demon_ctx *ctx, int n, float *predict_normal0);
 /* time `steps` back-to-back demon_run_full calls with hip events on the context stream */
@@ -280,6 +300,10 @@ int demon_op_scale_invariant_gradient(demon_ctx *ctx, float *out, const float *i
 int demon_op_median3x3_downsample(demon_ctx *ctx, float *out, const float *in, int nc, int h, int w);
 int demon_op_depth_to_normals(demon_ctx *ctx, float *out, const float *depth, const float *intrinsics, int n, int h, int w,
                               int inverse_depth);
+/* prepare_input_data of examples/example.py:15-42 for n pairs, host buffers in and out (the op-level form of demon_upload_images_u8;
+ * works on demon_create_ops contexts): image_pair [n,6,H,W], image2_2 [n,3,H/4,W/4] from uint8 [n,src_h,src_w,3]; H, W multiples of 32 */
+int demon_op_prepare_inputs_u8(demon_ctx *ctx, float *image_pair, float *image2_2, const uint8_t *image1, const uint8_t *image2, int n,
+                               int src_h, int src_w, int H, int W);
 /* pointwise_l2_loss of v2/losses.py:33-54 (NCHW): mean over pixels of sqrt(sum_c replace_nonfinite(inp - gt)^2 + epsilon) */
 int demon_op_pointwise_l2_loss(demon_ctx *ctx, float *loss, const float *inp, const float *gt, int n, int c, int h, int w,
                                float epsilon);
@@ -331,6 +355,12 @@ int demon_op_dense(demon_ctx *ctx, float *out, const float *in, const float *w_i
  * Not on the reference's path. */
 int demon_bench_layer(demon_ctx *ctx, int kind, int n, int cin, int h, int w, int cout, int kh, int kw, int sh,
                       int sw, int tile, int ksplit, int iters, float *avg_ms, double *flops);
+
+/* tools/ingest_bench.py: `iters` timings [ms] each (after `warmup` untimed rounds) of the ingest kernel over the first n staged pairs (what
+ * demon_upload_images_u8 launches, without its host-to-device copy; the resident inputs are overwritten) and, alternating with it, of one
+ * device-to-device hipMemcpyAsync of as many bytes as that kernel writes, by hip events on the context's stream.  Needs
+ * demon_ingest_configure.  Not on the reference's path. */
+int demon_bench_ingest(demon_ctx *ctx, int n, int warmup, int iters, float *kernel_ms, float *copy_ms);
 
 /* Poison harness (tests/test_poison_gpu.py).  With DEMON_POISON_GUARD=1 in the environment when a context is created (or when a
  * demon_op_conv2d / deconv4x4s2 / dense call runs), every device allocation -- activations, every weight form, workspaces -- is placed
