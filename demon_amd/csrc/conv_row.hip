@@ -17,6 +17,7 @@
 //     the two barriers per tile.  (Measured on the way: one tile per workgroup, U reloaded by each -- 75 us, the same as the general
 //     kernel; one persistent workgroup per CU with a double-buffered patch -- 81 us: with one wave per SIMD every LDS / barrier wait
 //     is exposed, PMC: matrix pipe 39 %, vector ALU 24 %, waiting 34 % of the wave cycles.)
+#include <algorithm>
 #include <type_traits>
 
 #include "internal.h"
@@ -217,7 +218,7 @@ static bool launch_row_t(const RowArgs &a, dim3 grid, size_t lds, hipStream_t s)
     return true;
 }
 
-bool launch_conv_row(RowArgs a, int taps, hipStream_t stream)
+bool launch_conv_row(RowArgs a, int taps, hipStream_t stream, int tpw_plan)
 {
     a.tiles_y = (a.Ho + ROW_R - 1) / ROW_R;
     a.tiles_x = (a.Wo + ROW_TX - 1) / ROW_TX;
@@ -226,10 +227,15 @@ bool launch_conv_row(RowArgs a, int taps, hipStream_t stream)
     const int ntiles = a.N * a.tiles_y * a.tiles_x;
     // a workgroup walks `tpw` tiles (stride = grid size) and retires: U is staged once per tpw tiles, and other streams' workgroups
     // get a CU's LDS every few microseconds (fully persistent workgroups -- two per CU for the whole launch -- were 4 us faster alone
-    // and gained nothing in the pipeline: the side stream's kernels could not start beside them)
-    static const int tpw_env = getenv("DEMON_ROW_TPW") ? atoi(getenv("DEMON_ROW_TPW")) : 0;
-    const int tpw = tpw_env > 0 ? tpw_env : 3;
-    const int wgs = (ntiles + tpw - 1) / tpw;
+    // and gained nothing in the pipeline: the side stream's kernels could not start beside them).  tpw_plan = the ksplit field of the
+    // layer's kind-13 plan entry: 0 and 1 = three tiles, kRowWholeLaunch = two workgroups per CU for the whole launch
+    // (any other value means three, as every value did while the field was ignored: an entry valid then launches what it launched)
+    const int tpw = (tpw_plan == 6 || tpw_plan == 12 || tpw_plan == kRowWholeLaunch) ? tpw_plan : 3;
+    int wgs = (ntiles + tpw - 1) / tpw;
+    if (tpw_plan == kRowWholeLaunch) {
+        static int cus = [] { hipDeviceProp_t p; int d = 0; return (hipGetDevice(&d) == hipSuccess && hipGetDeviceProperties(&p, d) == hipSuccess && p.multiProcessorCount > 0) ? p.multiProcessorCount : 256; }();
+        wgs = std::min(ntiles, 2 * (g_active_cus > 0 ? g_active_cus : cus));
+    }
     const dim3 grid((unsigned)(wgs < 1 ? 1 : wgs));
     const bool caffe = a.pad == taps / 2;
     if (taps == 9) return caffe ? launch_row_t<3, true>(a, grid, lds, stream) : launch_row_t<3, false>(a, grid, lds, stream);

@@ -69,7 +69,7 @@ struct Layer {
     float *d_w3 = nullptr;
     mutable bool w3_dirty = true;
     bool wino3_stride2() const { return kind == CONV && !scale && Cin >= 16 && kh == 3 && kw == 3 && sh == 2 && sw == 2 && ph == 1 && pw == 1; }
-    // four-outputs-per-window weights of the 3-tap stride-1 / 5-tap stride-2 1-D layers for conv_wino4.hip: U[e][Cin4][Mpad], 6 / 11 planes
+    // four-outputs-per-window weights of the 3-tap stride-1 / 5-, 7-, 9-tap stride-2 1-D layers for conv_wino4.hip: U[e][Cin4][Mpad], 6 / 11 / 13 / 15 planes
     float *d_w4 = nullptr;
     mutable bool w4_dirty = true;
     int wino4_kind_of() const
@@ -1010,7 +1010,8 @@ bool row_applies(const Layer *L)
            conv_row_shape_ok(L->kh, L->kw, L->sh, L->sw, L->ph, L->pw, L->Cin, L->Mpad, L->in.W, L->out.W);
 }
 
-bool run_row(const Layer *L, const ConvArgs &a, hipStream_t s)
+// ksplit field of the plan entry: tiles a workgroup walks before it retires (6, 12, kRowWholeLaunch = the whole launch; any other value: three)
+bool run_row(const Layer *L, const ConvArgs &a, hipStream_t s, int tpw = 0)
 {
     refresh_stream_weights(L, s);
     RowArgs r;
@@ -1018,7 +1019,7 @@ bool run_row(const Layer *L, const ConvArgs &a, hipStream_t s)
     r.N = a.N; r.Cin = L->Cin; r.Cin4 = L->Cin4(); r.H = a.H; r.W = a.W; r.in_n_stride = a.in_n_stride;
     r.Cout = L->Cout; r.Ho = a.Ho; r.Wo = a.Wo; r.out_n_stride = a.out_n_stride; r.out_plane = a.out_plane;
     r.pad = L->pw; r.act = a.act; r.tiles_y = r.tiles_x = 0;
-    if (!launch_conv_row(r, L->kw, s)) return false;
+    if (!launch_conv_row(r, L->kw, s, tpw)) return false;
     snprintf(g_kernel_tag, sizeof g_kernel_tag, "conv_row<32x128,t%d>", L->kw);
     g_last_kernel = g_kernel_tag;
     return true;
@@ -1087,7 +1088,7 @@ void run_layer(const Layer *L, int n, hipStream_t s, float *ws)
             } else if (kind == 16) {
                 if (run_wino4(L, a, tile, s, ks)) return;
             } else if (kind == 13) {
-                if (row_applies(L) && run_row(L, a, s)) return;
+                if (row_applies(L) && run_row(L, a, s, ks)) return;
             } else if (kind == 12) {
                 if (thin_applies(L) && run_thin(L, a, s)) return;
             } else if (kind == 11) {
@@ -1127,7 +1128,7 @@ void run_layer(const Layer *L, int n, hipStream_t s, float *ws)
             if (t.kind == 8 && wino_applies(L) && run_wino(L, a, t.tile, clamp_split(t.ksplit), s)) return;
             if (t.kind == 10 && wino1d_applies(L) && run_wino1d(L, a, t.tile, clamp_split(t.ksplit), s)) return;
             if (t.kind == 12 && thin_applies(L) && run_thin(L, a, s)) return;
-            if (t.kind == 13 && row_applies(L) && run_row(L, a, s)) return;
+            if (t.kind == 13 && row_applies(L) && run_row(L, a, s, t.ksplit)) return;
             if (t.kind == 15 && run_wino3(L, a, t.tile, s)) return;
             if (t.kind == 16 && run_wino4(L, a, t.tile, s, t.ksplit)) return;
             if (t.kind == 11 && dense_stream_applies(L) && run_dense_stream(L, a, t.tile, clamp_split(t.ksplit), s)) return;
@@ -1311,7 +1312,9 @@ int autotune_layer(demon_ctx *c, Layer *L, int n)
             }
         }
     }
-    if (wino4_applies(L)) {
+    // (the 7- / 9-tap kinds were measured with several passes in flight: offered in throughput mode only.  One replay at a time they also
+    // beat the first layer pair's second half, which flips autotune_fused_pair's one-launch-or-two choice on numbers nobody has confirmed)
+    if (wino4_applies(L) && (L->wino4_kind_of() <= 1 || c->opt_tune_lanes > 1)) {
         for (int v = 0; v < WINO4_VARIANTS; ++v) {
             Wino4Args w;
             if (fill_wino4_args(L, a, v, w) && wino4_workgroups(w, v) >= 128) {
@@ -1329,7 +1332,11 @@ int autotune_layer(demon_ctx *c, Layer *L, int n)
         }
     }
     if (thin_applies(L)) cands.push_back({12, 0, 1});
-    if (row_applies(L)) cands.push_back({13, 0, 1});
+    if (row_applies(L)) {
+        cands.push_back({13, 0, 1});
+        // throughput mode: no side stream needs a CU's LDS between this kernel's workgroups -- more tiles per staging of U
+        if (c->opt_tune_lanes > 1) for (int tpw : {6, 12, kRowWholeLaunch}) cands.push_back({13, 0, tpw});
+    }
     if (dense_stream_applies(L)) {
         const long blocks = (long)(L->Mpad / 128) * ((n + 31) / 32);
         for (int ks : {1, 2, 3, 4, 6, 8, 9, 12, 16, 18, 24, 32, 36, 48, 64}) {
@@ -2701,7 +2708,7 @@ int demon_plan_set(demon_ctx *c, int n, const char *layer_name, int kind, int ti
     // 13 = 1 x 7 / 1 x 9 stride-2 conv with <= 32 channels, whole reduction out of LDS (conv_row.hip; tile 0)
     // 14 = marker on the k x 1 layer of a conv_pair.hip pair: the fused launch was measured faster at this batch size (the layer alone: heuristics)
     // 15 = 3 x 3 stride-1 conv, transformed input rows stationary (conv_wino3.hip; tile = workgroup shape)
-    // 16 = k x 1 / 1 x k conv with four outputs per window (conv_wino4.hip: 3 taps stride 1, 5 taps stride 2; tile = workgroup shape)
+    // 16 = k x 1 / 1 x k conv with four outputs per window (conv_wino4.hip: 3 taps stride 1, 5 / 7 / 9 taps stride 2; tile = workgroup shape)
     if (kind < 0 || kind > 16 || kind == 2 || kind == 9 || tile < 0 ||
         tile >= (kind == 16 ? (int)WINO4_VARIANTS : kind == 15 ? (int)WINO3_VARIANTS : kind >= 12 ? 1 : kind == 11 ? (int)DENSE_VARIANTS : kind == 10 ? (int)WINO1D_VARIANTS : kind == 8 ? (int)WINO_VARIANTS : (kind == 1 ? (int)PTILE_COUNT : ((kind == 4 || kind == 7) ? (int)STREAM_VARIANTS : ((kind == 5 || kind == 6) ? (int)FRAG_VARIANTS : (int)TILE_COUNT)))) || ksplit < 0)
         return fail(c, DEMON_ERR_INVALID, "bad plan entry");
@@ -2713,7 +2720,7 @@ int demon_plan_set(demon_ctx *c, int n, const char *layer_name, int kind, int ti
             if (kind == 3 && !small_applies(L.get())) return fail(c, DEMON_ERR_INVALID, "the small-Cout kernel does not apply to this layer");
             if (kind == 8 && !wino_applies(L.get())) return fail(c, DEMON_ERR_INVALID, "the minimal-filtering kernel applies to transposed convs only");
             if (kind == 10 && !wino1d_applies(L.get())) return fail(c, DEMON_ERR_INVALID, "no 1-D minimal-filtering form for this layer");
-            if (kind == 16 && !wino4_applies(L.get())) return fail(c, DEMON_ERR_INVALID, "conv_wino4.hip applies to k x 1 / 1 x k convs with 3 taps stride 1 or 5 taps stride 2 and >= 16 input channels only");
+            if (kind == 16 && !wino4_applies(L.get())) return fail(c, DEMON_ERR_INVALID, "conv_wino4.hip applies to k x 1 / 1 x k convs with 3 taps stride 1 or 5 / 7 / 9 taps stride 2 and >= 16 input channels only");
             if (kind == 15 && !wino3_applies(L.get())) return fail(c, DEMON_ERR_INVALID, "conv_wino3.hip applies to 3 x 3 convs with >= 16 input channels, stride 1 (rows of even length) or stride 2 (rows of a multiple of 8 pixels, >= 64)");
             if (kind == 13 && !row_applies(L.get())) return fail(c, DEMON_ERR_INVALID, "conv_row.hip applies to 1 x 7 / 1 x 9 stride-2 convs with at most 32 channels on both sides only");
             if (kind == 12 && !thin_applies(L.get())) return fail(c, DEMON_ERR_INVALID, "conv_thin.hip applies to the 9 x 1 stride-2 first layer (Cin <= 6, Cout <= 32) only");

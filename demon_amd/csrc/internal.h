@@ -373,7 +373,7 @@ bool wino3_plan_geometry(Wino3Args &a, int variant);
 long wino3_workgroups(const Wino3Args &a, int variant);
 bool launch_wino3(const Wino3Args &a, int variant, hipStream_t stream);   // false: nothing was launched
 
-// ---- k x 1 / 1 x k convs with FOUR outputs per window: F(4,3) (3 taps, stride 1), F(4,3) + F(4,2) (5 taps, stride 2) (conv_wino4.hip) ----
+// ---- k x 1 / 1 x k convs with FOUR outputs per window: F(4,3) (3 taps, stride 1), F(4,3) + F(4,2) (5 taps, stride 2), F(4,4) + F(4,3) (7 taps, stride 2), F(4,5) + F(4,4) (9 taps, stride 2) (conv_wino4.hip) ----
 struct Wino4Args {
     const float *in;
     float *out;
@@ -397,12 +397,12 @@ struct Wino4Args {
     unsigned m_lines;                    // magic number of the division by lines_img
     int in_img_bytes, out_img_bytes;     // 4 in_n_stride, 4 out_n_stride (the host refuses batches whose last image would not fit a 31-bit offset)
 };
-constexpr int WINO4_VARIANTS = 14;   // workgroup shapes (waves along Cout x waves along positions x lines per wave x K groups per step); 9 ..: three lines per wave
-int wino4_kind(int taps, int stride);   // 0: 3 taps stride 1, 1: 5 taps stride 2, -1: none
+constexpr int WINO4_VARIANTS = 16;   // workgroup shapes (waves along Cout x waves along positions x lines per wave x K groups per step); 9 .. 13: three lines per wave; 14, 15: the 7- / 9-tap kinds only
+int wino4_kind(int taps, int stride);   // 0: 3 taps stride 1, 1 / 2 / 3: 5 / 7 / 9 taps stride 2, -1: none
 int wino4_nuv(int kind);
 int wino4_variant_bm(int v);
 int wino4_variant_kg(int v);
-bool wino4_variant_ok(int kind, int v);
+bool wino4_variant_ok(int kind, int v, int axis);
 bool wino4_plan_geometry(Wino4Args &a, int kind, int variant, int axis, bool flat = false);   // flat: false when it would not save a line block
 long wino4_workgroups(const Wino4Args &a, int variant);
 void launch_wino4_repack(float *wu, const float *wp, int kind, int Cin, int Cin4, int Mpad, hipStream_t s);
@@ -458,7 +458,8 @@ struct RowArgs {
     int tiles_y, tiles_x;   // (set by the launcher)
 };
 bool conv_row_shape_ok(int kh, int kw, int sh, int sw, int ph, int pw, int Cin, int Mpad, int W, int Wo);
-bool launch_conv_row(RowArgs a, int taps, hipStream_t stream);
+constexpr int kRowWholeLaunch = 1000;   // tiles per workgroup = this: workgroups that stay for the whole launch, two per CU
+bool launch_conv_row(RowArgs a, int taps, hipStream_t stream, int tiles_per_workgroup = 0);   // 6, 12, kRowWholeLaunch; anything else: three tiles
 
 // ---- tiny heads (conv_small.hip): VALU direct conv for Cout <= 4, fused motion tail -------------------------------------
 struct SmallConvArgs {

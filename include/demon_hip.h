@@ -117,7 +117,8 @@ int demon_autotune(demon_ctx *ctx, int n);
  *   11 weight-streaming kernel for the dense layers (dense_stream.hip: dense5 of v2, motion_fc1; tile 0 / 1 = default /
  *      non-temporal weight loads, ksplit = K slices), 12 the blocks' first layer (9 x 1, stride 2, <= 6 input channels) with the weights
  *      in registers (conv_thin.hip; tile 0) -- on that layer it also means: the conv1 pair runs as two launches, not as conv_pair.hip's one,
- *   13 1 x 7 / 1 x 9 stride-2 conv with at most 32 channels on both sides, whole reduction out of LDS (conv_row.hip; tile 0),
+ *   13 1 x 7 / 1 x 9 stride-2 conv with at most 32 channels on both sides, whole reduction out of LDS (conv_row.hip; tile 0; ksplit field = tiles a
+ *           workgroup walks before it retires: 6, 12, or 1000 (kRowWholeLaunch) = two workgroups per CU for the whole launch; every other value means three),
  *        3 small-Cout VALU kernel, 4 register-streaming kernel (conv_stream.hip), 5 fragment-tiled kernel (conv_frag.hip),
  *        6 / 7 on the k x 1 layer of a stride-1 pair: the pair runs as ONE chained launch of conv_frag / conv_stream variant `tile`;
  *        14 marker on the k x 1 layer of a conv_pair.hip pair: the fused launch measured faster at this batch size;
@@ -125,7 +126,8 @@ int demon_autotune(demon_ctx *ctx, int n);
  *           stride 1: tile = workgroup shape 0..7 on F(2,3) tiles, 8..15 on F(4,3) tiles; stride 2 (rows of a multiple of 8 pixels):
  *           tile 16..19, polyphase F(4,2) + F(4,1)),
  *        16 k x 1 / 1 x k conv with four outputs per window (conv_wino4.hip: F(4,3) for 3 taps stride 1, F(4,3) + F(4,2) for 5 taps
- *           stride 2; tile = workgroup shape 0..13; ksplit field = launch form: 1 one workgroup per tile, 2 tile-walking workgroups, 3 flat
+ *           stride 2, F(4,4) + F(4,3) for 7 taps and F(4,5) + F(4,4) for 9 taps stride 2 -- these two through plan entries only, the
+ *           heuristics never choose them; tile = workgroup shape 0..15; ksplit field = launch form: 1 one workgroup per tile, 2 tile-walking workgroups, 3 flat
  *           line order -- the lines of all images of the batch as one sequence, for maps whose lines per image do not fill a workgroup;
  *           a form that does not exist for the shape, or would save nothing, runs as form 1);
  *   tile = tile / variant id of that kernel; ksplit = K slices across workgroups, combined by a conv_splitk_reduce launch.

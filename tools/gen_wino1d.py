@@ -13,10 +13,11 @@ integer entries.  The script checks the identity AT [(G g) . (BT d)] = correlati
 """
 import os
 from fractions import Fraction as Fr
-from math import lcm
+from math import gcd, lcm
 
 POINTS = {2: [0, -1], 3: [0, 1, -1], 4: [0, 1, -1, 2], 5: [0, 1, -1, 2, -2], 1: []}   # F(2,r): r finite points (+ infinity)
-POINTS_BY_COUNT = {5: [0, 1, -1, 2, -2], 4: [0, 1, -1, 2]}                               # F(4,3) / F(4,2): m + r - 2 finite points
+POINTS_BY_COUNT = {5: [0, 1, -1, 2, -2], 4: [0, 1, -1, 2],                               # F(4,3) / F(4,2): m + r - 2 finite points
+                   6: [0, 1, -1, 2, -2, Fr(1, 2)], 7: [0, 1, -1, 2, -2, Fr(1, 2), Fr(-1, 2)]}   # F(4,4) / F(4,5): the 7- / 9-tap stride-2 kinds
 
 
 def toom(m, r):
@@ -107,6 +108,7 @@ def kind_matrices4(taps, stride):
             G[ne + i][2 * b + 1] = Go[i][b]
         for a_ in range(ro + 3):
             BT[ne + i][2 * a_ + 1] = BTo[i][a_]
+    AT, BT = integer_rows(AT, BT)   # (the points +-1/2 of the 7- / 9-tap kinds: a no-op for the others)
     return AT, G, BT, win
 
 
@@ -133,16 +135,23 @@ def render4(name, taps, stride, comment):
 
 def normalise(AT, G):
     """integer G: row e times its common denominator, column e of AT divided by it"""
+    return integer_rows(AT, G)
+
+
+def integer_rows(AT, M):
+    """integer M (G or BT) with rows in lowest terms: row e times its common denominator over the common factor of its numerators,
+    column e of AT divided by the same"""
     AT = [row[:] for row in AT]
-    G = [row[:] for row in G]
-    for e, row in enumerate(G):
+    M = [row[:] for row in M]
+    for e, row in enumerate(M):
         den = 1
         for v in row:
             den = lcm(den, v.denominator)
-        G[e] = [v * den for v in row]
+        scale = Fr(den, gcd(*[int(v * den) for v in row]) or 1)
+        M[e] = [v * scale for v in row]
         for k in range(len(AT)):
-            AT[k][e] = AT[k][e] / den
-    return AT, G
+            AT[k][e] = AT[k][e] / scale
+    return AT, M
 
 
 def check(AT, G, BT, taps, stride, win):
@@ -247,6 +256,8 @@ def render():
     out += render4("Wino43", 3, 1, "3 taps, stride 1, FOUR outputs per window of 6 inputs: 6 products instead of 12 (points 0, +-1, +-2, infinity)")
     out += render4("Wino4K5S2", 5, 2, "5 taps, stride 2, FOUR outputs per window of 11 inputs: polyphase F(4,3) + F(4,2) = 11 products instead of 20")
     out += render4("Wino4K3S2", 3, 2, "3 taps, stride 2, FOUR outputs per window of 9 inputs: polyphase F(4,2) + F(4,1) = 9 products instead of 12")
+    out += render4("Wino4K7S2", 7, 2, "7 taps, stride 2, FOUR outputs per window of 13 inputs: polyphase F(4,4) + F(4,3) = 13 products instead of 28 (points 0, +-1, +-2, 1/2, infinity)")
+    out += render4("Wino4K9S2", 9, 2, "9 taps, stride 2, FOUR outputs per window of 15 inputs: polyphase F(4,5) + F(4,4) = 15 products instead of 36 (points 0, +-1, +-2, +-1/2, infinity)")
     out.append("}  // namespace demon")
     return "\n".join(out) + "\n"
 

@@ -33,15 +33,19 @@ from demon_amd import DemonContext, weights as W  # noqa: E402
 from demon_amd.engine import DemonError  # noqa: E402
 
 FAMILY = {0: ("conv_mfma<",), 1: ("conv_patch<", "deconv4<"), 4: ("conv_stream<",), 5: ("conv_frag<",), 8: ("wino_deconv<",), 10: ("wino1d<",),
-          15: ("wino3rows<",), 16: ("wino4<",)}
+          13: ("conv_row<",), 15: ("wino3rows<",), 16: ("wino4<",)}
 SKIP_KINDS = (3, 6, 7, 11, 12, 13, 14)   # small-Cout, chained pairs (and their partners), dense stream, first-layer kernels: left alone
 
 
 def candidates(ks_list=(1, 2, 3, 4, 6, 8)):
     c = []
-    for v in range(14):
+    for v in range(16):
         for m in (1, 2, 3):
             c.append((16, v, m))
+    with open(os.path.join(ROOT, "demon_amd", "csrc", "internal.h")) as f:
+        whole = int(re.search(r"kRowWholeLaunch\s*=\s*(\d+)", f.read()).group(1))
+    for tpw in (1, 6, 12, whole):   # conv_row.hip: tiles a workgroup walks (one tag: the cheapest value is kept); --rows
+        c.append((13, 0, tpw))
     for v in range(13):
         for ks in ks_list:
             c.append((10, v, ks))
@@ -95,6 +99,7 @@ def main():
     ap.add_argument("--only", default="", help="comma-separated substrings of layer names (default: every layer with a plan entry of a tunable kind)")
     ap.add_argument("--kinds", default="", help="comma-separated plan kinds to draw candidates from (default: all)")
     ap.add_argument("--ks", default="1,2,3,4,6,8", help="split-K values tried on the kernels that have them (small batches: add 12,16,24,32)")
+    ap.add_argument("--rows", action="store_true", help="also re-tune the layers whose entry is conv_row.hip's (kind 13), which are left alone otherwise")
     ap.add_argument("--rounds", type=int, default=2)
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--margin", type=float, default=0.02, help="a candidate replaces the installed entry only if it is faster by this fraction in the confirmation round")
@@ -121,12 +126,13 @@ def main():
         ctx.set_option("side_branches", 0)   # (a lane of a group runs without them, demon_amd/lanes.py)
     base = ctx.get_plan(n)
     pats = [p for p in args.only.split(",") if p]
-    targets = [k for k, (kind, _, _) in base.items() if kind not in SKIP_KINDS and (not pats or any(p in k for p in pats))]
+    skip = tuple(k for k in SKIP_KINDS if not (args.rows and k == 13))
+    targets = [k for k, (kind, _, _) in base.items() if kind not in skip and (not pats or any(p in k for p in pats))]
     # the 1 x k partner of a chained pair has no launch of its own
     chained = {k[:-1] for k, (kind, _, _) in base.items() if kind in (6, 7)}
     targets = [k for k in targets if k[:-1] not in chained]
     kinds = {int(k) for k in args.kinds.split(",") if k}
-    cands = [c for c in candidates(tuple(int(k) for k in args.ks.split(","))) if not kinds or c[0] in kinds]
+    cands = [c for c in candidates(tuple(int(k) for k in args.ks.split(","))) if (not kinds or c[0] in kinds) and (args.rows or c[0] != 13)]
     print("plan %s, %d target layers, %d candidates, lanes %d" % (plan_file, len(targets), len(cands), L), flush=True)
 
     def profile(reps):

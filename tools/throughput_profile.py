@@ -32,6 +32,10 @@ def share(tag):
         return 0.5
     if tag.startswith("wino4<t5"):
         return 11 / 20
+    if tag.startswith("wino4<t7"):
+        return 13 / 28
+    if tag.startswith("wino4<t9"):
+        return 15 / 36
     m = re.match(r"(?:wino1d|wino3rows|conv_row<32x128,)<?t(\d+)", tag)
     if m:
         t = int(m.group(1))
