@@ -116,6 +116,9 @@ SIGNATURES = {
     "demon_op_deconv4x4s2": (_I, [_P, c_float_p, c_float_p, c_float_p, c_float_p] + [_I] * 6),
     "demon_op_dense": (_I, [_P, c_float_p, c_float_p, c_float_p, c_float_p] + [_I] * 4),
     "demon_op_point_cloud": (_I, [_P, c_float_p, c_float_p, c_uint8_p, c_int_p, c_float_p, c_float_p, c_uint8_p, c_float_p, c_float_p, c_float_p, c_float_p] + [_I] * 5),
+    "demon_op_view_pair": (_I, [_P, c_int_p, c_uint8_p, c_float_p] + [c_float_p] * 6 + [_I] * 6 + [_F, _F]),
+    "demon_op_view_pairs": (_I, [_P, c_int_p, c_uint8_p, c_float_p, c_float_p, c_int_p] + [c_float_p] * 4 + [_I] * 6 + [_F, _F]),
+    "demon_bench_view_pairs": (_I, [_P, c_int_p, c_uint8_p, c_float_p, c_float_p, c_int_p] + [c_float_p] * 4 + [_I] * 6 + [_F, _F, _I, _I, c_float_p]),
     "demon_bench_layer": (_I, [_P] + [_I] * 13 + [c_float_p, ctypes.POINTER(ctypes.c_double)]),
     "demon_bench_ingest": (_I, [_P, _I, _I, _I, c_float_p, c_float_p]),
     "demon_bench_cloud": (_I, [_P, _I, _I, _I, c_float_p]),

@@ -8,6 +8,10 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "libdemon_hip.so")
 SOURCES = ["demon_api.hip", "conv_mfma.hip", "conv_bf16.hip", "conv_patch.hip", "conv_small.hip", "conv_pair.hip", "conv_stream.hip", "conv_frag.hip", "conv_wino.hip", "conv_wino3.hip", "conv_wino4.hip", "dense_stream.hip", "conv_thin.hip", "conv_row.hip", "ops.hip", "ingest.hip", "pointcloud.hip"]
+# sources that are not on the network's path: compiled and linked like the others, but outside csrc_sha() -- the hash stamps the network's
+# profiles and its recorded dispatch trace (tests/golden/dispatch_trace.npz), which these files cannot change
+EXTRA_SOURCES = ["viewgeom.hip"]
+EXTRA_HEADERS = ["viewgeom.h"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function", "-Wno-unused-value", "-Wno-unused-result"]
 
 
@@ -46,9 +50,10 @@ def build(force=False, verbose=False, extra_flags=(), tag=""):
     hipcc = _hipcc()
     out = OUT if not tag else OUT.replace(".so", "_%s.so" % tag)
     headers = [os.path.join(CSRC, "internal.h"), os.path.join(CSRC, "wino1d_tables.h"), os.path.join(HERE, "..", "include", "demon_hip.h")]
+    headers += [os.path.join(CSRC, n) for n in EXTRA_HEADERS]
     objs = []
     jobs = []
-    for src in SOURCES:
+    for src in SOURCES + EXTRA_SOURCES:
         s = os.path.join(CSRC, src)
         o = os.path.join(CSRC, src.replace(".hip", (".%s.o" % tag) if tag else ".o"))
         objs.append(o)

@@ -25,6 +25,7 @@
 
 #include "../../include/demon_hip.h"
 #include "internal.h"
+#include "viewgeom.h"
 
 using namespace demon;
 
@@ -3534,6 +3535,107 @@ int demon_op_point_cloud(demon_ctx *c, float *points, float *normals, uint8_t *c
     if (colors) HIP_TRY(c, hipMemcpy(colors, a.colors, 3 * rows, hipMemcpyDeviceToHost));
     if (counts) HIP_TRY(c, hipMemcpy(counts, d_counts, sizeof(int) * n, hipMemcpyDeviceToHost));
     return DEMON_OK;
+}
+
+// one or many pairs of views (viewgeom.hip).  depth1 holds `planes1` maps of h x w, depth2 `planes2` maps of H2 x W2 (null: no ratios);
+// one_set: depth2 is depth1 (the same maps, same size), uploaded once.  pairs == null: the one pair (0, 0).  kernel_ms != null:
+// demon_bench_view_pairs.
+static int view_pairs_impl(demon_ctx *c, int *counts, uint8_t *mask, float *ratios, const float *depth1, int planes1, const float *depth2,
+                           int planes2, bool one_set, const int *pairs, const float *K1, const float *R1, const float *t1, const float *P2, int n,
+                           int h, int w, int H2, int W2, int borderx, int bordery, float lo, float hi, int warmup, int iters, float *kernel_ms)
+{
+    OP_PROLOGUE(c);
+    if (!depth1 || !K1 || !R1 || !t1 || !P2) return fail(c, DEMON_ERR_INVALID, "null input pointer (depth, K1, R1, t1, P2)");
+    if (n < 1 || planes1 < 1 || !view_shape_ok(h, w, H2, W2))
+        return fail(c, DEMON_ERR_INVALID, "bad shape (n, views, h, w, height2, width2 >= 1; h * w <= 2^30; height2 * width2 <= 2^30)");
+    if (ratios && !depth2) return fail(c, DEMON_ERR_INVALID, "ratios output without a depth map of view 2");
+    if (borderx < 0 || bordery < 0) return fail(c, DEMON_ERR_INVALID, "negative border");
+    if (kernel_ms && (warmup < 0 || iters < 1)) return fail(c, DEMON_ERR_INVALID, "bad argument");
+    if (pairs)
+        for (long i = 0; i < 2l * n; ++i)
+            if (pairs[i] < 0 || pairs[i] >= ((i & 1) && depth2 ? planes2 : planes1)) return fail(c, DEMON_ERR_INVALID, "pair " + std::to_string(i / 2) + " names a view outside the set");
+    const size_t hw = (size_t)h * w, hw2 = (size_t)H2 * W2, px = (size_t)n * hw;
+    const int chunks = view_chunks(h, w);
+    std::vector<float> rec((size_t)kViewRecord * n);
+    for (int i = 0; i < n; ++i)
+        view_pack_record(K1 + 9l * i, R1 + 9l * i, t1 + 3l * i, P2 + 12l * i, W2, H2, borderx, bordery, lo, hi, pairs ? pairs[2l * i] : 0, pairs ? pairs[2l * i + 1] : 0,
+                         rec.data() + (size_t)kViewRecord * i);
+    ViewArgs a{};
+    float *d_depth1 = tmp.upload(depth1, planes1 * hw), *d_rec = tmp.upload(rec.data(), rec.size());
+    int *d_chunks = (int *)tmp.alloc((size_t)n * chunks * 4), *d_counts = (int *)tmp.alloc((size_t)n * 4);
+    if (!d_depth1 || !d_rec || !d_chunks || !d_counts) return fail(c, DEMON_ERR_HIP, "temporary device allocation failed");
+    a.depth1 = d_depth1; a.plane1_stride = (long)hw;
+    if (depth2) {
+        a.depth2 = one_set ? d_depth1 : tmp.upload(depth2, planes2 * hw2);
+        a.plane2_stride = (long)hw2;
+        if (!a.depth2) return fail(c, DEMON_ERR_HIP, "temporary device allocation failed");
+    }
+    uint8_t *d_mask = mask ? (uint8_t *)tmp.alloc((px + 3) / 4) : nullptr;
+    float *d_ratios = ratios ? tmp.alloc(px) : nullptr;
+    if ((mask && !d_mask) || (ratios && !d_ratios)) return fail(c, DEMON_ERR_HIP, "temporary device allocation failed");
+    a.h = h; a.w = w; a.H2 = H2; a.W2 = W2;
+    constexpr int kBatch = 32768;    // grid.y is the pair
+    auto enqueue = [&] {
+        for (int first = 0; first < n; first += kBatch) {
+            ViewArgs b = a;
+            b.n = std::min(kBatch, n - first);
+            b.records = d_rec + (size_t)kViewRecord * first;
+            b.mask = d_mask ? d_mask + (size_t)first * hw : nullptr;
+            b.ratios = d_ratios ? d_ratios + (size_t)first * hw : nullptr;
+            b.chunk_counts = d_chunks + (size_t)first * chunks * 4;
+            b.counts = d_counts + 4l * first;
+            launch_view_pairs(b, c->stream);
+        }
+    };
+    enqueue();
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (mask) HIP_TRY(c, hipMemcpy(mask, d_mask, px, hipMemcpyDeviceToHost));
+    if (ratios) HIP_TRY(c, hipMemcpy(ratios, d_ratios, sizeof(float) * px, hipMemcpyDeviceToHost));
+    if (counts) HIP_TRY(c, hipMemcpy(counts, d_counts, sizeof(int) * 4 * (size_t)n, hipMemcpyDeviceToHost));
+    if (!kernel_ms) return DEMON_OK;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) { if (e0) hipEventDestroy(e0); return fail(c, DEMON_ERR_HIP, "hipEventCreate failed"); }
+    int rc = DEMON_OK;
+    for (int i = 0; i < warmup + iters && rc == DEMON_OK; ++i) {
+        hipError_t e = hipEventRecord(e0, c->stream);
+        if (e == hipSuccess) { enqueue(); e = hipGetLastError(); }
+        if (e == hipSuccess) e = hipEventRecord(e1, c->stream);
+        if (e == hipSuccess) e = hipEventSynchronize(e1);
+        float ms = 0.0f;
+        if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
+        if (e != hipSuccess) rc = fail(c, DEMON_ERR_HIP, std::string("demon_bench_view_pairs: ") + hipGetErrorString(e));
+        else if (i >= warmup) kernel_ms[i - warmup] = ms;
+    }
+    hipEventDestroy(e0);
+    hipEventDestroy(e1);
+    return rc;
+}
+
+int demon_op_view_pair(demon_ctx *c, int *counts, uint8_t *mask, float *ratios, const float *depth1, const float *depth2, const float *K1,
+                       const float *R1, const float *t1, const float *P2, int h, int w, int height2, int width2, int borderx, int bordery,
+                       float ratio_lo, float ratio_hi)
+{
+    return view_pairs_impl(c, counts, mask, ratios, depth1, 1, depth2, 1, false, nullptr, K1, R1, t1, P2, 1, h, w, height2, width2, borderx, bordery,
+                           ratio_lo, ratio_hi, 0, 0, nullptr);
+}
+
+int demon_op_view_pairs(demon_ctx *c, int *counts, uint8_t *mask, float *ratios, const float *depth, const int *pairs, const float *K1,
+                        const float *R1, const float *t1, const float *P2, int nviews, int n, int h, int w, int borderx, int bordery,
+                        float ratio_lo, float ratio_hi)
+{
+    if (c && !pairs) return fail(c, DEMON_ERR_INVALID, "null input pointer (pairs)");
+    return view_pairs_impl(c, counts, mask, ratios, depth, nviews, depth, nviews, true, pairs, K1, R1, t1, P2, n, h, w, h, w, borderx, bordery, ratio_lo,
+                           ratio_hi, 0, 0, nullptr);
+}
+
+int demon_bench_view_pairs(demon_ctx *c, int *counts, uint8_t *mask, float *ratios, const float *depth, const int *pairs, const float *K1,
+                           const float *R1, const float *t1, const float *P2, int nviews, int n, int h, int w, int borderx, int bordery,
+                           float ratio_lo, float ratio_hi, int warmup, int iters, float *kernel_ms)
+{
+    if (c && (!pairs || !kernel_ms)) return fail(c, DEMON_ERR_INVALID, "null pointer (pairs, kernel_ms)");
+    return view_pairs_impl(c, counts, mask, ratios, depth, nviews, depth, nviews, true, pairs, K1, R1, t1, P2, n, h, w, h, w, borderx, bordery, ratio_lo,
+                           ratio_hi, warmup, iters, kernel_ms);
 }
 
 int demon_op_flow_to_depth(demon_ctx *c, float *out, const float *flow, const float *intrinsics, const float *rotation,

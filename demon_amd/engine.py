@@ -413,6 +413,60 @@ class DemonContext:
         clouds = _trim_clouds(*self.point_cloud_buffers(depth, K, R, t, normals, colors, image, inverse_depth, color_rounding))
         return clouds[0] if single else clouds
 
+    # ---- view tools (viewgeom.hip) ----------------------------------------------------------------------------
+    def view_pair(self, depth1, depth2, K1, R1, t1, P2, width2=None, height2=None, borderx=0, bordery=0, ratio_lo=0.0, ratio_hi=float("inf"),
+                  want_mask=True, want_ratios=True):
+        """demon_op_view_pair: depth1 [h,w]; depth2 [H2,W2] or None (then width2 / height2 size the mask; no ratios); K1, R1 [3,3],
+        t1 [3], P2 [3,4] in float32.  Returns (mask uint8 [h,w] or None, ratios float32 [h,w] or None, counts int32 [4])."""
+        depth1 = _f32(depth1)
+        if depth1.ndim != 2:
+            raise DemonError("depth1 has shape %s, expected [h,w]" % (tuple(depth1.shape),))
+        h, w = (int(v) for v in depth1.shape)
+        if depth2 is not None:
+            depth2 = _f32(depth2)
+            if depth2.ndim != 2:
+                raise DemonError("depth2 has shape %s, expected [h,w]" % (tuple(depth2.shape),))
+            height2, width2 = (int(v) for v in depth2.shape)
+        elif want_ratios:
+            raise DemonError("ratios need the depth map of view 2")
+        elif width2 is None or height2 is None:
+            raise DemonError("without depth2, width2 and height2 must be given")
+        K1, R1, t1, P2 = _f32(K1, (3, 3), "K1"), _f32(R1, (3, 3), "R1"), _f32(np.reshape(t1, -1), (3,), "t1"), _f32(P2, (3, 4), "P2")
+        mask = np.empty((h, w), np.uint8) if want_mask else None
+        ratios = np.empty((h, w), np.float32) if want_ratios else None
+        counts = np.empty(4, np.int32)
+        self._check(self.lib.demon_op_view_pair(
+            self.h, counts.ctypes.data_as(c_int_p), None if mask is None else _u8p(mask), None if ratios is None else _fp(ratios), _fp(depth1),
+            None if depth2 is None else _fp(depth2), _fp(K1), _fp(R1), _fp(t1), _fp(P2), h, w, int(height2), int(width2), int(borderx), int(bordery),
+            float(ratio_lo), float(ratio_hi)))
+        return mask, ratios, counts
+
+    def view_pairs(self, depth, pairs, K1, R1, t1, P2, borderx=0, bordery=0, ratio_lo=0.0, ratio_hi=float("inf"), want_mask=False, want_ratios=False,
+                   bench=None):
+        """demon_op_view_pairs: depth [V,h,w] uploaded once, pairs [n,2] int32 into it, K1, R1 [n,9], t1 [n,3], P2 [n,12] per pair.
+        Returns (counts int32 [n,4], mask uint8 [n,h,w] or None, ratios float32 [n,h,w] or None).  bench=(warmup, iters): also returns
+        the hip-event times [ms] of the two launches (demon_bench_view_pairs)."""
+        depth = _f32(depth)
+        if depth.ndim != 3:
+            raise DemonError("depth has shape %s, expected [views,h,w]" % (tuple(depth.shape),))
+        V, h, w = (int(v) for v in depth.shape)
+        pairs = np.ascontiguousarray(pairs, dtype=np.int32)
+        if pairs.ndim != 2 or pairs.shape[1] != 2 or pairs.shape[0] < 1:
+            raise DemonError("pairs has shape %s, expected [n,2]" % (tuple(pairs.shape),))
+        n = int(pairs.shape[0])
+        K1, R1, t1, P2 = (_f32(np.reshape(a, (n, -1)), (n, k), name) for a, k, name in ((K1, 9, "K1"), (R1, 9, "R1"), (t1, 3, "t1"), (P2, 12, "P2")))
+        counts = np.empty((n, 4), np.int32)
+        mask = np.empty((n, h, w), np.uint8) if want_mask else None
+        ratios = np.empty((n, h, w), np.float32) if want_ratios else None
+        args = (self.h, counts.ctypes.data_as(c_int_p), None if mask is None else _u8p(mask), None if ratios is None else _fp(ratios), _fp(depth),
+                pairs.ctypes.data_as(c_int_p), _fp(K1), _fp(R1), _fp(t1), _fp(P2), V, n, h, w, int(borderx), int(bordery), float(ratio_lo), float(ratio_hi))
+        if bench is None:
+            self._check(self.lib.demon_op_view_pairs(*args))
+            return counts, mask, ratios
+        ms = np.zeros(int(bench[1]), np.float32)
+        self._check(self.lib.demon_bench_view_pairs(*(args + (int(bench[0]), int(bench[1]), _fp(ms)))))
+        return counts, mask, ratios, ms.tolist()
+
     def configure_cloud(self, intrinsics=None, color_rounding="reference"):
         """demon_cloud_configure: the point-cloud buffers for max_batch images; K from four normalised intrinsics (default: the
         sun3d ones of vis.py:252), R = I, t = 0.  Nothing may be in flight."""

@@ -3,6 +3,8 @@
 * `median_downsample_image2` -- image2_2 as evaluation.py:173 builds it (two 3x3-median downsamples, HIP kernel)
 * `predict_pair`             -- the 4-stage prediction loop of evaluation.py:225-256 (bootstrap, 3 x iterative, refinement
                                 after every stage) returning what create_prediction_file stores per sample
+* `invalidate_points_not_visible_in_second_image` -- the `depthmask` step of evaluation/evaluate_to_xarray.py:92-121 (visibility
+                                mask on the GPU, demon_amd.view_tools)
 * depth / motion metrics     -- numpy restatement of the formulas of python/depthmotionnet/evaluation/metrics.py
                                 (:40-237 depth errors after Eigen et al., :282-321 scale factor, :390-445 motion errors);
                                 the reference module needs minieigen, which is not installable here.
@@ -169,3 +171,32 @@ def flow_epe(flow1, flow2):
     epe = np.sqrt(np.square(f1 - f2).sum(0))
     m = valid_depth_mask(epe)
     return np.nan if not m.any() else epe[m].mean()
+
+
+# ---- depthmask (evaluate_to_xarray.py:92-121) --------------------------------------------------------------------
+def invalidate_points_not_visible_in_second_image(depth, motion, intrinsics=None):
+    """Sets the depth values for the points not visible in the second view to nan, in place (evaluate_to_xarray.py:92-121).
+
+    depth: float32 array [h,w] (or with leading axes of length 1) with inverse depth values as stored in the test output h5 files;
+    motion: the 6 element motion vector (angle axis, translation); intrinsics: the normalized intrinsics vector, None for sun3d's.
+    1 / depth is taken in float32 numpy, K in double from the intrinsics, view 1 is (I, 0), view 2 comes from the motion through
+    _rotmat (the reference goes through minieigen there), and the mask is compute_visible_points_mask on the GPU."""
+    from .view_tools import View, compute_visible_points_mask
+    if not isinstance(depth, np.ndarray) or depth.dtype != np.float32:
+        raise ValueError("depth must be a float32 numpy array (it is changed in place)")
+    h, w = depth.shape[-2:]
+    plane = depth.reshape(h, w)          # raises when the leading axes are not of length 1
+    if not np.shares_memory(plane, depth):
+        raise ValueError("depth must be contiguous in its last two axes")
+    with np.errstate(divide="ignore", invalid="ignore"):
+        abs_depth = 1 / plane
+    tmp = np.asarray(motion).squeeze().astype(np.float64)
+    R, t = _rotmat(tmp[0:3]), tmp[3:].copy()
+    if intrinsics is None:
+        intrinsics = np.array([[0.891, 1.188, 0.5, 0.5]], dtype=np.float32)   # sun3d intrinsics
+    k = np.asarray(intrinsics).squeeze().astype(np.float64)
+    K = np.array([k[0] * w, 0, k[2] * w, 0, k[1] * h, k[3] * h, 0, 0, 1], dtype=np.float64).reshape((3, 3))
+    view1 = View(R=np.eye(3), t=np.zeros((3,)), K=K, image=None, depth=abs_depth, depth_metric='camera_z')
+    view2 = View(R=R, t=t, K=K, image=None, depth=abs_depth, depth_metric='camera_z')
+    invalid_points = compute_visible_points_mask(view1, view2) == 0
+    plane[invalid_points] = np.nan

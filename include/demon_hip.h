@@ -343,6 +343,33 @@ int demon_op_prepare_inputs_u8(demon_ctx *ctx, float *image_pair, float *image2_
 int demon_op_point_cloud(demon_ctx *ctx, float *points, float *normals, uint8_t *colors, int *counts, const float *depth,
                          const float *normals_in, const uint8_t *colors_u8_in, const float *image_in, const float *K, const float *R,
                          const float *t, int n, int h, int w, int inverse_depth, int color_rounding);
+/* The view tools of python/depthmotionnet/dataset_tools/view_tools_cython.pyx on the GPU (viewgeom.hip), host buffers in and out, on
+ * demon_create_ops contexts too.  Per pixel of view 1 they are the float32 operations of `_compute_visible_points_mask`
+ * (view_tools_cython.pyx:34-56) and `_compute_depth_ratios` (:129-157) in their order, one rounding each, without fused multiply-adds,
+ * the lookup rounded half to even (Python's round, :152-153) and clamped to [0, W2] / [0, H2] as there: masks and ratios are the
+ * reference's bit for bit.  The reference reads depth2 with bounds checks off; a lookup whose flat index y2 * W2 + x2 is at or past
+ * H2 * W2 is outside the map and gives "no ratio" here.  K1, R1 [3,3], t1 [3], P2 [3,4] are the float32 arrays that
+ * compute_visible_points_mask / compute_depth_ratios hand down (:81-84, :93-98, :180-191).
+ *   mask   uint8, 1 where the pixel's depth is finite and > 0 and its projection lies in front of view 2 and strictly inside
+ *          (borderx, width2 - borderx) x (bordery, height2 - bordery); 0 elsewhere
+ *   ratios float32, projected z / depth2 at the looked-up pixel; the quiet NaN 0x7fc00000 where there is none.  Never another NaN.
+ *   counts int32 x 4: pixels of view 1 with valid depth | mask == 1 | finite ratios | finite ratios with ratio_lo < ratio < ratio_hi
+ *          (the numbers check_depth_consistency, view_tools.py:82-94, decides on: dr.size is h * w)
+ * NULL outputs are skipped; every element of a non-NULL output is written.
+ *
+ * demon_op_view_pair: one pair.  depth1 [h,w]; depth2 [height2,width2] or NULL (mask and the first two counts only; width2 / height2 are
+ * then what view_tools_cython.pyx:86-91 passes).  ratios needs depth2.  Both maps are uploaded in their own sizes; depth1 and depth2 may
+ * point at the same host memory.
+ * demon_op_view_pairs: n ordered pairs out of a set depth [nviews,h,w], uploaded once: pairs [n,2] int32 (view 1, view 2; an index outside
+ * [0, nviews) returns DEMON_ERR_INVALID before anything is launched or written), K1, R1 [n,9], t1 [n,3], P2 [n,12] per pair; mask,
+ * ratios [n,h,w], counts [n,4].  With mask and ratios NULL nothing but the counts leaves the device: the pair mining of
+ * dataset_tools/sun3d_utils.py:186-212. */
+int demon_op_view_pair(demon_ctx *ctx, int *counts, uint8_t *mask, float *ratios, const float *depth1, const float *depth2, const float *K1,
+                       const float *R1, const float *t1, const float *P2, int h, int w, int height2, int width2, int borderx, int bordery,
+                       float ratio_lo, float ratio_hi);
+int demon_op_view_pairs(demon_ctx *ctx, int *counts, uint8_t *mask, float *ratios, const float *depth, const int *pairs, const float *K1,
+                        const float *R1, const float *t1, const float *P2, int nviews, int n, int h, int w, int borderx, int bordery,
+                        float ratio_lo, float ratio_hi);
 /* pointwise_l2_loss of v2/losses.py:33-54 (NCHW): mean over pixels of sqrt(sum_c replace_nonfinite(inp - gt)^2 + epsilon) */
 int demon_op_pointwise_l2_loss(demon_ctx *ctx, float *loss, const float *inp, const float *gt, int n, int c, int h, int w,
                                float epsilon);
@@ -404,6 +431,12 @@ int demon_bench_ingest(demon_ctx *ctx, int n, int warmup, int iters, float *kern
 /* tools/cloud_bench.py: `iters` timings [ms] (after `warmup` untimed rounds) of the two launches demon_run_cloud enqueues for the first n
  * resident predictions, by hip events on the context's stream.  Needs demon_cloud_configure.  Not on the reference's path. */
 int demon_bench_cloud(demon_ctx *ctx, int n, int warmup, int iters, float *kernel_ms);
+
+/* tools/view_geom_bench.py: demon_op_view_pairs, and then `iters` timings [ms] (after `warmup` untimed rounds) of its two launches on the
+ * uploaded set, by hip events on the context's stream.  Not on the reference's path. */
+int demon_bench_view_pairs(demon_ctx *ctx, int *counts, uint8_t *mask, float *ratios, const float *depth, const int *pairs, const float *K1,
+                           const float *R1, const float *t1, const float *P2, int nviews, int n, int h, int w, int borderx, int bordery,
+                           float ratio_lo, float ratio_hi, int warmup, int iters, float *kernel_ms);
 
 /* Poison harness (tests/test_poison_gpu.py).  With DEMON_POISON_GUARD=1 in the environment when a context is created (or when a
  * demon_op_conv2d / deconv4x4s2 / dense call runs), every device allocation -- activations, every weight form, workspaces -- is placed
